@@ -10,9 +10,13 @@ Multi-GPU (torchrun, one process per GPU): the graph is replicated and the roots
 are sharded across ranks (Graph500-style source sharding, no data-path
 collective) -> weak scaling.
 
-At N=1 the same line also carries `secondary` results: configs[1] (Kronecker s22
-unit weights, direction-optimizing BFS) and configs[0] (web-Google-shaped
-synthetic, source 0). Inputs are generated on the device (no dataset access).
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline figure needs:
+it builds the graph, warms up, times the K steps and prints the line. `--dump-outputs DIR`
+also writes what the last timed step computed (DIR/dist.npy, see dump_outputs). Every other
+leg runs only with `--full`: the time-to-solution process, the CPU baseline, the partitioned
+legs, and at N=1 the `secondary` results: configs[1] (Kronecker s22 unit weights,
+direction-optimizing BFS) and configs[0] (web-Google-shaped synthetic, source 0). Inputs
+are generated on the device (no dataset access), the same for the same arguments.
 
   value        = GTEPS = sum over ranks of m_r / max-over-ranks wall time of the
                  timed steps; m_r = CSR entries of the reached vertices
@@ -24,7 +28,7 @@ synthetic, source 0). Inputs are generated on the device (no dataset access).
                  the calibrated DRAM-side bytes of the per-kernel table measured on
                  this build (profiles/traffic_k26w.json, else null); frac_model_8d
                  keeps SURVEY.md §8d's every-reached-edge model
-  cpu_baseline = the reference's BSP heap algorithm (oracle port of :466-594,
+  cpu_baseline = (--full) the reference's BSP heap algorithm (oracle port of :466-594,
                  weights honoured) on host threads, rank 0 at N=1 only, on a
                  bounded sample of one solve of the same graph
 """
@@ -87,8 +91,25 @@ def make_graph(ctx, wl, args):
     return ctx.generate_kronecker(scale, args.edgefactor, args.seed, weighted=wl["weighted"])
 
 
-def run_workload(ctx, key, args, rank, world, barrier, steps, warmup):
-    """Timed SSSPs of one workload on this rank; returns per-rank sums."""
+DUMP_MAX = 1 << 22  # entries of a dumped array (16 MB as float32)
+
+
+def dump_outputs(g, seed, out_dir):
+    """--dump-outputs: the distances of the graph's last solve, as a caller reads them
+    (pj_copy_dist: input ids, INT_INF = unreached), to out_dir/dist.npy as float32 (exact:
+    every distance is <= INT_INF < 2^24). A result of more than DUMP_MAX entries is
+    sampled at np.random.default_rng(seed).integers(0, n, DUMP_MAX), sorted: the same
+    vertices in every run with the same arguments."""
+    d = g.copy_dist()
+    if d.size > DUMP_MAX:
+        d = d[np.sort(np.random.default_rng(seed).integers(0, d.size, DUMP_MAX))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "dist.npy"), d.astype(np.float32))
+
+
+def run_workload(ctx, key, args, rank, world, barrier, steps, warmup, dump_dir=None):
+    """Timed SSSPs of one workload on this rank; returns per-rank sums. With dump_dir the
+    last timed solve's distances are written there (dump_outputs), after the timed region."""
     import paralleljohnson_amd as pj
     wl = WORKLOADS[key]
     t_gen = time.perf_counter()
@@ -116,6 +137,8 @@ def run_workload(ctx, key, args, rank, world, barrier, steps, warmup):
         g.stats_into(sts[k])
     barrier()
     elapsed = time.perf_counter() - t0
+    if dump_dir:
+        dump_outputs(g, args.seed, dump_dir)
     kernel_ms = [st.kernel_ms for st in sts]
     work = [(st.scanned_edges, st.probes, st.work_bytes) for st in sts]
     reach, levels = {}, {}
@@ -477,11 +500,17 @@ def launch_check(rank, world, backend):
         dist.destroy_process_group()
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=16)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline figure: the time-to-solution process, the CPU "
+                         "baseline, the secondary workloads and the partitioned legs (each still has its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the distances of the last timed step to DIR/dist.npy (float32; a fixed seeded "
+                         "sample of a large result), rank 0")
     ap.add_argument("--workload", default="k26w", choices=sorted(WORKLOADS))
     ap.add_argument("--scale", type=int, default=0, help="override the Kronecker scale (testing only)")
     ap.add_argument("--edgefactor", type=int, default=16)
@@ -501,7 +530,16 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="test only: start the ranks, rendezvous, barrier and the max/sum reductions of the line, "
                          "no GPU work (the CPU test of the --gpus launch path)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_tts = args.no_cpu_baseline = args.no_secondary = args.no_partitioned = True
+    return args
+
+
+def main():
+    args = parse_args()
 
     # --gpus N means N ranks, one process per GPU (the reference's `mpirun -np P`, README:9).
     # Without a launcher (no WORLD_SIZE) this process starts them itself, before anything here
@@ -551,7 +589,8 @@ def main():
         # made right then wait for it (seen as 1-3 s of "graph build" in whichever process
         # allocated next), so the GPU is left idle for a few seconds before this one builds
         time.sleep(5.0)
-    main_res = run_workload(ctx, args.workload, args, rank, world, barrier, args.steps, args.warmup)
+    main_res = run_workload(ctx, args.workload, args, rank, world, barrier, args.steps, args.warmup,
+                            dump_dir=args.dump_outputs if rank == 0 else None)
     elapsed, m_sum, b_sum, t_kernel = main_res["elapsed"], main_res["m_sum"], main_res["b_sum"], main_res["t_kernel"]
     w_sum, scanned, probes = main_res["w_sum"], main_res["scanned"], main_res["probes"]
     if dist is not None:

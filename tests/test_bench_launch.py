@@ -85,3 +85,48 @@ def test_transport_guard_accepts_only_a_full_rccl_group():
             assert "needs an RCCL communicator of 4 ranks" in str(e)
         else:
             raise AssertionError((kind, n))
+
+
+def test_plain_run_times_the_steps_only_and_full_restores_the_legs():
+    """A plain `--gpus 1 --steps K --warmup W` run switches every leg beyond the headline figure
+    off; `--full` runs them again, each still under its own --no-* switch."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    legs = ("no_tts", "no_cpu_baseline", "no_secondary", "no_partitioned")
+    a = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (3, 1, False, None)
+    assert all(getattr(a, k) for k in legs)
+    f = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--dump-outputs", "d"])
+    assert f.full and f.dump_outputs == "d" and not any(getattr(f, k) for k in legs)
+    f = bench.parse_args(["--full", "--no-tts"])
+    assert f.no_tts and not f.no_secondary
+
+
+def test_dump_outputs_writes_a_fixed_float32_sample(tmp_path):
+    """--dump-outputs: the whole result when it is small, else the same seeded sample of
+    DUMP_MAX entries in every run, as float32 (exact for distances <= INT_INF)."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class G:
+        def __init__(self, d):
+            self.d = d
+
+        def copy_dist(self):
+            return self.d
+
+    small = np.arange(1000, dtype=np.int32)
+    bench.dump_outputs(G(small), 1, str(tmp_path / "s"))
+    got = np.load(tmp_path / "s" / "dist.npy")
+    assert got.dtype == np.float32 and (got == small).all()
+    big = (np.arange(bench.DUMP_MAX + 12345, dtype=np.int64) * 7919 % 100001).astype(np.int32)
+    for name in ("a", "b"):
+        bench.dump_outputs(G(big), 1, str(tmp_path / name))
+    a, b = np.load(tmp_path / "a" / "dist.npy"), np.load(tmp_path / "b" / "dist.npy")
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_MAX,) and a.nbytes <= 64 << 20
+    assert (a == b).all()
+    idx = np.sort(np.random.default_rng(1).integers(0, big.size, bench.DUMP_MAX))
+    assert (a == big[idx]).all()

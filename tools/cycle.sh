@@ -4,7 +4,7 @@
 # STEPS: comma-separated, run in order, stopping at the first failure:
 #   tests         every -m gpu test           tests:<pytest args>  e.g. tests:tests/test_gpu_parity.py
 #   smoke         __graft_entry__.smoke()
-#   bench         the default bench line (bench args appended) -> bench.json
+#   bench         the full bench line, bench.py --full (bench args appended) -> bench.json
 #   kt            rocprofv3 kernel trace + stats of a short k26w bench run
 #   calib         FETCH_SIZE calibration: tools/calib/pj_gather_calib timed, then under --pmc (one counter
 #                 group per run) -> calib.log, calpmc_*/, gather_calib.json (tools/calib_table.py)
@@ -45,7 +45,7 @@ for st in "${LIST[@]}"; do
         || { echo "smoke failed"; tail "$OUT/smoke.log"; exit 1; }
       tail -2 "$OUT/smoke.log" ;;
     bench)
-      timeout -k 10 500 python -u bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" \
+      timeout -k 10 500 python -u bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" \
         || { echo "bench failed"; tail -20 "$OUT/bench.err"; exit 1; }
       python3 -c "import json,sys; d=json.load(open(sys.argv[1])); s=d.get('secondary',{}); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d.get('time_to_solution_s'), (d.get('time_to_solution_phases') or {}).get('process_phases'), s.get('wg',{}).get('ms_per_sssp'), s.get('ms1024',{}).get('batch_ms'))" "$OUT/bench.json" ;;
     kt)

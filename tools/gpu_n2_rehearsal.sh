@@ -5,6 +5,6 @@
 set -o pipefail
 OUT=gpurun_out/n2; mkdir -p $OUT
 PJ_BENCH_BACKEND=gloo timeout -k 10 500 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-  --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 8 --warmup 1 "$@" \
+  --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 8 --warmup 1 "$@" \
   > $OUT/bench.json 2> $OUT/bench.err || { echo bench n2 failed; tail -30 $OUT/bench.err; exit 1; }
 cat $OUT/bench.json
