@@ -40,7 +40,8 @@ enum pj_status {
     PJ_ERR_RANGE = -6,    /* id / size outside the supported range */
     PJ_ERR_NODEVICE = -7, /* no usable gfx950 device */
     PJ_ERR_STATE = -8,    /* call out of order (e.g. stats before a solve) */
-    PJ_ERR_COMM = -9      /* RCCL / multi-GPU error */
+    PJ_ERR_COMM = -9,     /* RCCL / multi-GPU error */
+    PJ_ERR_NEGCYCLE = -10 /* the graph has a negative-weight cycle */
 };
 
 typedef struct pj_ctx pj_ctx;
@@ -116,6 +117,63 @@ int pj_load_snap_buffer(pj_ctx* ctx, const char* text, int64_t len, int weighted
  * edge counts may exceed 2^31 (64-bit offsets are used then). */
 int pj_load_coo(pj_ctx* ctx, const int64_t* src, const int64_t* dst, const uint32_t* w,
                 int64_t nnz, int64_t n_vertices, pj_graph** out);
+
+/* ---- signed edge weights: the first half of Johnson's algorithm ------------
+ *
+ * No reference counterpart (the reference hard-codes w = 1, :147). A signed loader
+ * accepts int32 weights of either sign, computes on the GPU the Bellman-Ford
+ * potentials h[v] = min(0, min over u of d(u, v)) (the fixpoint from h = 0
+ * everywhere, the virtual-source formulation; potential.hip), and builds the graph
+ * from the reduced weights w'(u, v) = w(u, v) + h[u] - h[v] >= 0. The result is a
+ * weighted graph whose distances are the TRUE signed distances: the solvers run
+ * unchanged on w' and give d'(s, v) = d(s, v) + h[s] - h[v]; a correction pass maps
+ * every row to
+ *
+ *   out[v] = PJ_INT_INF              if d'(s, v) >= PJ_INT_INF (the solver's cap, in reduced space)
+ *          = PJ_INT_INF              if d(s, v)  >= PJ_INT_INF (the rule of every distance here)
+ *          = d'(s, v) - h[s] + h[v]  otherwise (may be negative)
+ *
+ * in pj_sssp, pj_copy_dist, pj_dist_device, pj_sssp_batch and pj_sssp_batch_write;
+ * pj_reach_stats counts the vertices with out[v] < PJ_INT_INF, and pj_set_option and the
+ * automatic delta work as on any weighted graph (the mean weight is that of w').
+ * The original weights are not stored: pj_graph_get_csr returns the reduced weights
+ * (rows sorted by them); the input weight of an entry u -> v is w' - h[u] + h[v].
+ * pj_parent_tree and pj_validate_tree run in reduced space (dist[u] + w == dist[v]
+ * is invariant under the reweighting), which agrees with their definition stated in
+ * the true weights, parent[v] = -1 exactly where out[v] = PJ_INT_INF; when the last
+ * solve has a vertex with d' < PJ_INT_INF <= d (reached by the solver, reported
+ * unreached) both return PJ_ERR_RANGE, since such a vertex could be a parent.
+ * Refused on a signed graph: pj_graph_save and pj_wpart_from_graph return
+ * PJ_ERR_ARG (the cache format and the partitions carry no potentials), and the
+ * n-GPU handle has no signed entry (its loaders reject a negative weight as before).
+ *
+ * A negative-weight cycle fails the load with PJ_ERR_NEGCYCLE (the last error text
+ * names a vertex on the cycle); a potential below -2^30 fails it with PJ_ERR_RANGE.
+ * st may be NULL; it is filled on PJ_ERR_NEGCYCLE as well, and *out is then NULL.
+ * Device memory during a signed load, besides the 12 bytes per entry of the edge list:
+ * 24 bytes per entry while the rounds' rows are sorted, 8 per entry and 12 per vertex
+ * (offsets, keys) plus three n-bit frontiers during the rounds; all of it is freed
+ * before the graph's own arrays are built, and 4 bytes per vertex (h) stay. */
+typedef struct pj_potential_stats {
+    double kernel_ms;       /* device time of the Bellman-Ford rounds + the reweighting */
+    int64_t rounds;         /* relaxation rounds run (0 when no weight is negative) */
+    int64_t relaxed_edges;  /* edge records read by the rounds */
+    int64_t negative_edges; /* input entries with w < 0 */
+    int64_t cycle_checks;   /* predecessor-cycle checks run */
+    int64_t cycle_vertex;   /* a vertex ON a negative cycle (PJ_ERR_NEGCYCLE), else -1 */
+    int32_t min_potential;  /* min h[v] (<= 0) */
+} pj_potential_stats;
+
+/* As pj_load_coo with int32 weights (w is required); |w| must fit int32 (PJ_ERR_RANGE). */
+int pj_load_coo_signed(pj_ctx* ctx, const int64_t* src, const int64_t* dst, const int32_t* w, int64_t nnz,
+                       int64_t n_vertices, pj_potential_stats* st, pj_graph** out);
+/* The pj_load_snap grammar with a third column that may carry a sign; a missing third
+ * field reads as 0; a weight whose magnitude does not fit int32 is PJ_ERR_PARSE. */
+int pj_load_snap_signed(pj_ctx* ctx, const char* path, pj_potential_stats* st, pj_graph** out);
+int pj_load_snap_buffer_signed(pj_ctx* ctx, const char* text, int64_t len, pj_potential_stats* st, pj_graph** out);
+/* The potentials h (n int32, host); PJ_ERR_STATE on a graph of any other loader. */
+int pj_graph_potentials(const pj_graph* g, int32_t* h_out);
+int pj_graph_is_signed(const pj_graph* g, int* out);
 
 /* Binary CSR cache (no reference counterpart: the
  * reference re-parses the text on every run, read_webgraph :66-105 +

@@ -43,7 +43,7 @@ _lib = ctypes.CDLL(LIB_PATH)
 PJ_OK = 0
 _STATUS = {
     -1: "PJ_ERR_ARG", -2: "PJ_ERR_IO", -3: "PJ_ERR_PARSE", -4: "PJ_ERR_HIP", -5: "PJ_ERR_OOM",
-    -6: "PJ_ERR_RANGE", -7: "PJ_ERR_NODEVICE", -8: "PJ_ERR_STATE", -9: "PJ_ERR_COMM",
+    -6: "PJ_ERR_RANGE", -7: "PJ_ERR_NODEVICE", -8: "PJ_ERR_STATE", -9: "PJ_ERR_COMM", -10: "PJ_ERR_NEGCYCLE",
 }
 
 
@@ -52,6 +52,7 @@ class PJError(RuntimeError):
         super().__init__(f"{_STATUS.get(code, code)}: {msg}")
         self.code = code
         self.name = _STATUS.get(code, str(code))
+        self.potential_stats = None  # dict, when a signed load failed with PJ_ERR_NEGCYCLE
 
 
 class Stats(ctypes.Structure):
@@ -75,6 +76,15 @@ class TreeReport(ctypes.Structure):
                                               "bad_cycle")]
 
 
+class PotentialStats(ctypes.Structure):
+    _fields_ = [("kernel_ms", ctypes.c_double), ("rounds", ctypes.c_int64), ("relaxed_edges", ctypes.c_int64),
+                ("negative_edges", ctypes.c_int64), ("cycle_checks", ctypes.c_int64),
+                ("cycle_vertex", ctypes.c_int64), ("min_potential", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class LoadStats(ctypes.Structure):
     _fields_ = [("read_ms", ctypes.c_double), ("h2d_ms", ctypes.c_double), ("parse_ms", ctypes.c_double),
                 ("csr_ms", ctypes.c_double), ("text_bytes", ctypes.c_int64)]
@@ -96,6 +106,11 @@ _SIGS = {
     "pj_load_snap": ([_P, ctypes.c_char_p, _INT, _PP], _INT),
     "pj_load_snap_buffer": ([_P, ctypes.c_char_p, _I64, _INT, _PP], _INT),
     "pj_load_coo": ([_P, _P, _P, _P, _I64, _I64, _PP], _INT),
+    "pj_load_coo_signed": ([_P, _P, _P, _P, _I64, _I64, _P, _PP], _INT),
+    "pj_load_snap_signed": ([_P, ctypes.c_char_p, _P, _PP], _INT),
+    "pj_load_snap_buffer_signed": ([_P, ctypes.c_char_p, _I64, _P, _PP], _INT),
+    "pj_graph_potentials": ([_P, _P], _INT),
+    "pj_graph_is_signed": ([_P, _P], _INT),
     "pj_generate_kronecker": ([_P, _INT, _INT, ctypes.c_uint64, _INT, _PP], _INT),
     "pj_generate_webgraph": ([_P, _I64, _I64, ctypes.c_uint64, _PP], _INT),
     "pj_kronecker_write_snap": ([_P, _INT, _INT, ctypes.c_uint64, _INT, ctypes.c_char_p], _INT),
@@ -234,6 +249,10 @@ class Graph:
         n, m, w, s = _I64(), _I64(), _INT(), _INT()
         _check(_lib.pj_graph_info(self._h, ctypes.byref(n), ctypes.byref(m), ctypes.byref(w), ctypes.byref(s)))
         self.n, self.nnz, self.weighted, self.symmetric = n.value, m.value, bool(w.value), bool(s.value)
+        sg = _INT()
+        _check(_lib.pj_graph_is_signed(self._h, ctypes.byref(sg)))
+        self.is_signed = bool(sg.value)  # loaded with signed weights: distances are true signed distances
+        self._potential_stats = None
 
     def close(self):
         if self._h:
@@ -327,6 +346,18 @@ class Graph:
         _check(_lib.pj_validate_tree(self._h, int(source), _ptr(p), ctypes.byref(rep)))
         return {k: getattr(rep, k) for k, _ in rep._fields_}
 
+    # -- signed graphs (Context.load_*_signed) -----------------------------------
+    def potentials(self) -> np.ndarray:
+        """The Bellman-Ford potentials h (int32, <= 0) of a signed graph; get_csr() then holds the
+        reduced weights w' = w + h[u] - h[v] >= 0. PJ_ERR_STATE on any other graph."""
+        out = np.empty(max(self.n, 1), np.int32)
+        _check(_lib.pj_graph_potentials(self._h, _ptr(out)))
+        return out[: self.n]
+
+    def potential_stats(self) -> Optional[dict]:
+        """pj_potential_stats of the signed load (None for any other graph)."""
+        return None if self._potential_stats is None else dict(self._potential_stats)
+
     # -- inspection --------------------------------------------------------
     def save(self, path: str, src_size: int = -1, src_mtime_ns: int = -1):
         """Binary CSR cache of this graph (pj_graph_save)."""
@@ -398,6 +429,36 @@ class Context:
         g = ctypes.c_void_p()
         _check(_lib.pj_load_coo(self._h, _ptr(s), _ptr(d), _ptr(wa), len(s), int(n), ctypes.byref(g)))
         return Graph(self, g)
+
+    def _signed(self, call) -> Graph:
+        g, st = ctypes.c_void_p(), PotentialStats()
+        rc = call(ctypes.byref(st), ctypes.byref(g))
+        if rc != PJ_OK:
+            err = PJError(rc, (_lib.pj_last_error() or b"").decode(errors="replace"))
+            if err.name == "PJ_ERR_NEGCYCLE":
+                err.potential_stats = st.as_dict()
+            raise err
+        out = Graph(self, g)
+        out._potential_stats = st.as_dict()
+        return out
+
+    def load_coo_signed(self, src, dst, w, n: int = -1) -> Graph:
+        """A graph with signed int32 weights (pj_load_coo_signed): Bellman-Ford potentials on the GPU,
+        then the usual weighted graph on the reduced weights; solves return true signed distances.
+        PJError PJ_ERR_NEGCYCLE (with .potential_stats) when the graph has a negative cycle."""
+        s = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
+        d = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
+        wa = np.ascontiguousarray(np.asarray(w, dtype=np.int32))
+        if len(s) != len(d) or len(s) != len(wa):
+            raise ValueError("src, dst and w differ in length")
+        return self._signed(lambda st, g: _lib.pj_load_coo_signed(self._h, _ptr(s), _ptr(d), _ptr(wa), len(s),
+                                                                   int(n), st, g))
+
+    def load_snap_signed(self, path: str) -> Graph:
+        return self._signed(lambda st, g: _lib.pj_load_snap_signed(self._h, os.fsencode(path), st, g))
+
+    def load_snap_buffer_signed(self, text: bytes) -> Graph:
+        return self._signed(lambda st, g: _lib.pj_load_snap_buffer_signed(self._h, text, len(text), st, g))
 
     def load_snap_cached(self, path: str, cache_path: Optional[str], weighted: bool = False,
                          write_back: bool = True) -> Graph:

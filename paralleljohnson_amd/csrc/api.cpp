@@ -227,6 +227,45 @@ void parse_error(const ParseResult& r) {
               "(undefined behaviour in the reference's read_webgraph)");
 }
 
+// The last single-source row as the caller sees it: g.dist in input ids; on a signed graph its
+// back-transform into true distances (g.dist_true, made once per solve; g.dist keeps the reduced
+// distances that the tree and reach kernels read together with the reduced weights).
+const int32_t* result_dist(Graph& g) {
+    delta_materialize(g);
+    if (!g.is_signed) return g.dist.p;
+    if (!g.true_valid) {
+        hipStream_t s = g.ctx->stream;
+        g.dist_true.ensure((size_t)std::max<i64>(g.n, 1));
+        g.true_cnt.ensure(1);
+        PJ_HIP(hipMemsetAsync(g.true_cnt.p, 0, sizeof(u64), s));
+        signed_correct(g.dist.p, g.h.p, g.n, g.last_source, g.dist_true.p, g.true_cnt.p,
+                       (unsigned)g.ctx->cu_count * 8u, s);
+        u64 c = 0;
+        PJ_HIP(hipMemcpyAsync(&c, g.true_cnt.p, sizeof(u64), hipMemcpyDeviceToHost, s));
+        PJ_HIP(hipStreamSynchronize(s));
+        g.true_capped = (i64)c;
+        g.true_valid = true;
+    }
+    return g.dist_true.p;
+}
+
+// signed graphs: the tree is built in reduced space (tightness is invariant under the
+// reweighting); a vertex reached there but reported unreached (d >= PJ_INT_INF) would be a parent
+bool tree_refused(Graph& g, const char* who) {
+    if (!g.is_signed) return false;
+    (void)result_dist(g);
+    if (g.true_capped == 0) return false;
+    set_error(std::string(who) + ": " + std::to_string(g.true_capped) +
+              " vertices are reached on the reduced weights but their distance is >= PJ_INT_INF");
+    return true;
+}
+
+// on_row of a weighted batch on a signed graph: the device row into true distances, in place
+void correct_batch_row(Graph& g, int64_t source, const int32_t* dev, hipStream_t s) {
+    if (g.is_signed)
+        signed_correct(dev, g.h.p, g.n, source, const_cast<int32_t*>(dev), nullptr, (unsigned)g.ctx->cu_count * 8u, s);
+}
+
 int finish_graph(pj_ctx* ctx, std::unique_ptr<pj_graph>& pg, pj_graph** out) {
     (void)ctx;
     *out = pg.release();
@@ -522,6 +561,158 @@ int pj_load_coo(pj_ctx* ctx, const int64_t* src, const int64_t* dst, const uint3
     });
 }
 
+// ---- signed weights: Bellman-Ford potentials, then the usual build on the reduced weights ----
+
+namespace {
+
+void negcycle_error(const pj_potential_stats& st) {
+    set_error(st.cycle_vertex >= 0
+                  ? "the graph has a negative-weight cycle through vertex " + std::to_string(st.cycle_vertex)
+                  : std::string("the graph has a negative-weight cycle (no fixpoint after n rounds)"));
+}
+
+// device COO with int32 weights -> potentials, reduced weights, graph. The rounds' CSR and the
+// COO are gone when this returns (the COO is consumed by the build).
+int signed_graph_from_coo(pj_ctx* ctx, DevBuf<u32>& src, DevBuf<u32>& dst, DevBuf<u32>& w, i64 nnz, i64 n,
+                          pj_potential_stats* st, std::unique_ptr<pj_graph>& pg) {
+    pg = std::make_unique<pj_graph>();
+    Graph& g = pg->g;
+    g.ctx = &ctx->c;
+    pj_potential_stats ps{};
+    if ((size_t)nnz > w.n) w.alloc((size_t)nnz);
+    const int rc = signed_potentials(ctx->c, src.p, dst.p, w.p, nnz, n, g.h, ps);
+    if (st) *st = ps;
+    if (rc == PJ_ERR_NEGCYCLE) negcycle_error(ps);
+    else if (rc == PJ_ERR_RANGE) set_error("signed load: a potential fell below -2^30");
+    if (rc != PJ_OK) {
+        pg.reset();
+        return rc;
+    }
+    build_graph_from_coo(g, src, dst, &w, nnz, n, false);
+    g.is_signed = true;
+    return PJ_OK;
+}
+
+int signed_from_parse(pj_ctx* ctx, const ParseResult& r, DevBuf<u32>& src, DevBuf<u32>& dst, DevBuf<u32>& w,
+                      int64_t len, pj_potential_stats* st, pj_graph** out) {
+    if (r.bad_line) {
+        set_error("edge list line " + std::to_string(r.bad_line) +
+                  ": second field missing, negative id, id out of range or a weight outside int32");
+        return (int)PJ_ERR_PARSE;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    std::unique_ptr<pj_graph> pg;
+    const int rc = signed_graph_from_coo(ctx, src, dst, w, r.nnz, r.max_id + 1, st, pg);
+    if (rc != PJ_OK) return rc;
+    PJ_HIP(hipStreamSynchronize(ctx->c.stream));
+    pg->g.load.csr_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    pg->g.load.h2d_ms = r.h2d_ms;
+    pg->g.load.parse_ms = r.parse_ms;
+    pg->g.load.text_bytes = len;
+    return finish_graph(ctx, pg, out);
+}
+
+void clear_pot_stats(pj_potential_stats* st) {
+    if (!st) return;
+    *st = pj_potential_stats{};
+    st->cycle_vertex = -1;
+}
+
+}  // namespace
+
+int pj_load_coo_signed(pj_ctx* ctx, const int64_t* src, const int64_t* dst, const int32_t* w, int64_t nnz,
+                       int64_t n_vertices, pj_potential_stats* st, pj_graph** out) {
+    if (!ctx || !out || nnz < 0 || (nnz > 0 && (!src || !dst || !w))) return arg_error("pj_load_coo_signed: bad argument");
+    *out = nullptr;
+    clear_pot_stats(st);
+    return guarded([&] {
+        bind(ctx->c);
+        std::vector<u32> hs((size_t)nnz), hd((size_t)nnz);
+        i64 mx = -1;
+        for (i64 i = 0; i < nnz; ++i) {
+            const i64 a = src[i], b = dst[i];
+            if (a < 0 || b < 0 || a > 0xFFFFFFFEll || b > 0xFFFFFFFEll) {
+                set_error("pj_load_coo_signed: vertex id out of range at edge " + std::to_string(i));
+                return (int)PJ_ERR_RANGE;
+            }
+            if (w[i] == INT32_MIN) {
+                set_error("pj_load_coo_signed: |w| must fit int32 (edge " + std::to_string(i) + ")");
+                return (int)PJ_ERR_RANGE;
+            }
+            hs[(size_t)i] = (u32)a;
+            hd[(size_t)i] = (u32)b;
+            mx = std::max(mx, std::max(a, b));
+        }
+        i64 n = n_vertices < 0 ? mx + 1 : n_vertices;
+        if (n <= mx || n > 0xFFFFFFFFll) {
+            set_error("pj_load_coo_signed: n_vertices must exceed every id and fit 32 bits");
+            return (int)PJ_ERR_RANGE;
+        }
+        hipStream_t s = ctx->c.stream;
+        DevBuf<u32> ds((size_t)nnz), dd((size_t)nnz), dw((size_t)nnz);
+        if (nnz) {
+            PJ_HIP(hipMemcpyAsync(ds.p, hs.data(), 4 * (size_t)nnz, hipMemcpyHostToDevice, s));
+            PJ_HIP(hipMemcpyAsync(dd.p, hd.data(), 4 * (size_t)nnz, hipMemcpyHostToDevice, s));
+            PJ_HIP(hipMemcpyAsync(dw.p, w, 4 * (size_t)nnz, hipMemcpyHostToDevice, s));
+        }
+        PJ_HIP(hipStreamSynchronize(s));
+        std::unique_ptr<pj_graph> pg;
+        const int rc = signed_graph_from_coo(ctx, ds, dd, dw, nnz, n, st, pg);
+        if (rc != PJ_OK) return rc;
+        return finish_graph(ctx, pg, out);
+    });
+}
+
+int pj_load_snap_buffer_signed(pj_ctx* ctx, const char* text, int64_t len, pj_potential_stats* st, pj_graph** out) {
+    if (!ctx || !out || (len > 0 && !text) || len < 0) return arg_error("pj_load_snap_buffer_signed: bad argument");
+    *out = nullptr;
+    clear_pot_stats(st);
+    return guarded([&] {
+        bind(ctx->c);
+        DevBuf<u32> src, dst, w;
+        ParseResult r = parse_snap_device(ctx->c, text, len, true, src, dst, w, true);
+        return signed_from_parse(ctx, r, src, dst, w, len, st, out);
+    });
+}
+
+int pj_load_snap_signed(pj_ctx* ctx, const char* path, pj_potential_stats* st, pj_graph** out) {
+    if (!ctx || !path || !out) return arg_error("pj_load_snap_signed: bad argument");
+    *out = nullptr;
+    clear_pot_stats(st);
+    return guarded([&] {
+        bind(ctx->c);
+        const auto t0 = std::chrono::steady_clock::now();
+        DevBuf<uint8_t> text;
+        const i64 len = read_file_to_device(ctx->c, path, text);
+        const double read_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        DevBuf<u32> src, dst, w;
+        ParseResult r = parse_device_text(ctx->c, text.p, len, true, src, dst, w, true);
+        text.release();
+        const int rc = signed_from_parse(ctx, r, src, dst, w, len, st, out);
+        if (rc == PJ_OK) (*out)->g.load.read_ms = read_ms;
+        return rc;
+    });
+}
+
+int pj_graph_is_signed(const pj_graph* g, int* out) {
+    if (!g || !out) return arg_error("pj_graph_is_signed: bad argument");
+    *out = g->g.is_signed ? 1 : 0;
+    return PJ_OK;
+}
+
+int pj_graph_potentials(const pj_graph* pg, int32_t* h_out) {
+    if (!pg || (!h_out && pg->g.n > 0)) return arg_error("pj_graph_potentials: bad argument");
+    if (!pg->g.is_signed) {
+        set_error("pj_graph_potentials: the graph was not loaded through a signed loader");
+        return PJ_ERR_STATE;
+    }
+    return guarded([&] {
+        bind(*pg->g.ctx);
+        if (pg->g.n) PJ_HIP(hipMemcpy(h_out, pg->g.h.p, 4 * (size_t)pg->g.n, hipMemcpyDeviceToHost));
+        return (int)PJ_OK;
+    });
+}
+
 int pj_generate_kronecker(pj_ctx* ctx, int scale, int edgefactor, uint64_t seed, int weighted, pj_graph** out) {
     if (!ctx || !out || scale < 0 || scale > 31 || edgefactor < 1 || edgefactor > 1024)
         return arg_error("pj_generate_kronecker: scale must be in [0,31], edgefactor in [1,1024]");
@@ -695,10 +886,8 @@ int pj_sssp(pj_graph* pg, int64_t source, int32_t* dist_out) {
         if (g.weighted) delta_solve(g, source);
         else bfs_solve(g, source);
         g.last_source = source;
-        if (dist_out && g.n) {
-            delta_materialize(g);
-            copy_d2h_staged(*g.ctx, dist_out, g.dist.p, 4 * (size_t)g.n);
-        }
+        g.true_valid = false;
+        if (dist_out && g.n) copy_d2h_staged(*g.ctx, dist_out, result_dist(g), 4 * (size_t)g.n);
         g.stats.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         return (int)PJ_OK;
     });
@@ -712,8 +901,8 @@ int pj_copy_dist(pj_graph* pg, int32_t* dist_out) {
     }
     return guarded([&] {
         bind(*pg->g.ctx);
-        delta_materialize(pg->g);
-        if (pg->g.n) copy_d2h_staged(*pg->g.ctx, dist_out, pg->g.dist.p, 4 * (size_t)pg->g.n);
+        const int32_t* d = result_dist(pg->g);
+        if (pg->g.n) copy_d2h_staged(*pg->g.ctx, dist_out, d, 4 * (size_t)pg->g.n);
         return (int)PJ_OK;
     });
 }
@@ -736,12 +925,13 @@ int pj_host_unpin(void* p) {
 
 const int32_t* pj_dist_device(pj_graph* pg) {
     if (!pg || !pg->g.have_result) return nullptr;
+    const int32_t* d = nullptr;
     const int rc = guarded([&] {
         bind(*pg->g.ctx);
-        delta_materialize(pg->g);  // (complete when it returns)
+        d = result_dist(pg->g);  // (complete when it returns)
         return (int)PJ_OK;
     });
-    return rc == PJ_OK ? pg->g.dist.p : nullptr;
+    return rc == PJ_OK ? d : nullptr;
 }
 
 // ---- shortest-path tree (tree.hip) ---------------------------------------------
@@ -755,6 +945,7 @@ int pj_parent_tree(pj_graph* pg, int64_t* parent_out) {
     return guarded([&] {
         bind(*pg->g.ctx);
         delta_materialize(pg->g);
+        if (tree_refused(pg->g, "pj_parent_tree")) return (int)PJ_ERR_RANGE;
         parent_tree(pg->g, pg->g.last_source, parent_out);
         return (int)PJ_OK;
     });
@@ -769,6 +960,7 @@ int pj_validate_tree(pj_graph* pg, int64_t source, const int64_t* parent, pj_tre
     return guarded([&] {
         bind(*pg->g.ctx);
         delta_materialize(pg->g);
+        if (tree_refused(pg->g, "pj_validate_tree")) return (int)PJ_ERR_RANGE;
         validate_tree(pg->g, source, parent, out);
         return (int)PJ_OK;
     });
@@ -810,6 +1002,7 @@ int pj_sssp_batch(pj_graph* pg, const int64_t* sources, int n_src, int32_t* dist
         if (g.weighted) {
             delta_batch(g, sources, n_src, g.batch_streams, [&](int i, const int32_t* dev, hipStream_t s) {
                 if (dist_out && g.n) {
+                    correct_batch_row(g, sources[i], dev, s);
                     PJ_HIP(hipMemcpyAsync(dist_out + (size_t)i * (size_t)g.n, dev, 4 * (size_t)g.n,
                                           hipMemcpyDeviceToHost, s));
                     PJ_HIP(hipStreamSynchronize(s));
@@ -837,7 +1030,10 @@ int pj_sssp_batch_write(pj_graph* pg, const int64_t* sources, int n_src, const c
         if (g.weighted) {
             // concurrent solves (delta_batch); rows are gathered into host groups and written by the pool
             delta_batch(g, sources, n_src, g.batch_streams,
-                        [&](int i, const int32_t* dev, hipStream_t s) { wr.add_row(i, dev, s); });
+                        [&](int i, const int32_t* dev, hipStream_t s) {
+                            correct_batch_row(g, sources[i], dev, s);
+                            wr.add_row(i, dev, s);
+                        });
         } else {
             msbfs_each(g, sources, n_src, [&](int off, int ns, const int32_t* rows) {
                 for (int k = 0; k < ns; ++k) wr.add_row(off + k, rows + (size_t)k * n);
@@ -873,8 +1069,7 @@ int pj_reach_stats(pj_graph* pg, pj_stats* out) {
     return guarded([&] {
         bind(*pg->g.ctx);
         i64 nr = 0, mr = 0;
-        delta_materialize(pg->g);
-        reach_stats(pg->g, &nr, &mr);
+        reach_stats(pg->g, &nr, &mr, result_dist(pg->g));
         pg->g.stats.reached = nr;
         pg->g.stats.reached_edges = mr;
         if (out) *out = pg->g.stats;
@@ -982,6 +1177,7 @@ uint64_t csr_payload(int64_t n, int64_t nnz, uint32_t flags) {
 
 int pj_graph_save(const pj_graph* pg, const char* path, int64_t src_size, int64_t src_mtime_ns) {
     if (!pg || !path) return arg_error("pj_graph_save: bad argument");
+    if (pg->g.is_signed) return arg_error("pj_graph_save: a signed graph cannot be saved (the cache format carries no potentials)");
     return guarded([&] {
         const Graph& g = pg->g;
         bind(*g.ctx);
@@ -1201,6 +1397,7 @@ int pj_wpart_from_graph(pj_graph* g, int rank, int world, pj_wpart** out) {
     if (!g || !out) return arg_error("pj_wpart_from_graph: bad argument");
     if (world < 1 || world > 64 || rank < 0 || rank >= world)
         return arg_error("pj_wpart_from_graph: need 0 <= rank < world <= 64");
+    if (g->g.is_signed) return arg_error("pj_wpart_from_graph: a signed graph cannot be partitioned (no potentials there)");
     *out = nullptr;
     return guarded([&] {
         bind(*g->g.ctx);

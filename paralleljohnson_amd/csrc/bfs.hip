@@ -1441,14 +1441,15 @@ void bfs_solve(Graph& g, i64 source) {
     else bfs_run<u32>(g, *g.bfs_work, source);
 }
 
-void reach_stats(Graph& g, i64* n_r, i64* m_r) {
+void reach_stats(Graph& g, i64* n_r, i64* m_r, const int32_t* dist) {
     hipStream_t s = g.ctx->stream;
+    if (!dist) dist = g.dist.p;
     DevBuf<u64> out(2);
     PJ_HIP(hipMemsetAsync(out.p, 0, 2 * sizeof(u64), s));
     const unsigned grid = grid_for(g.n, 256, (unsigned)g.ctx->cu_count * 8u);
     if (g.n > 0) {
-        if (g.off64) reach_k<u64><<<grid, 256, 0, s>>>(g.dist.p, g.n, g.row64.p, out.p);
-        else reach_k<u32><<<grid, 256, 0, s>>>(g.dist.p, g.n, g.row32.p, out.p);
+        if (g.off64) reach_k<u64><<<grid, 256, 0, s>>>(dist, g.n, g.row64.p, out.p);
+        else reach_k<u32><<<grid, 256, 0, s>>>(dist, g.n, g.row32.p, out.p);
         PJ_LAUNCH_CHECK();
     }
     u64 h[2];

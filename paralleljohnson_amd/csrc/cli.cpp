@@ -21,7 +21,11 @@
 // PJ_WEIGHTED=1 (third column = weight, delta-stepping), PJ_CSR_CACHE (binary
 // CSR cache: "1" for <webfile>.pjcsr, or a path; loaded instead of parsing when
 // its stamp -- the text's size and mtime -- and weight mode match, else written
-// after the parse; P = 1 only), PJ_PHASES=1 (phase times on stderr).
+// after the parse; P = 1 only), PJ_PHASES=1 (phase times on stderr), PJ_SIGNED=1 (implies
+// PJ_WEIGHTED: the third column may be negative; Bellman-Ford potentials and Johnson's
+// reweighting at the load, true signed distances in the sol_file; single source or
+// PJ_SOURCES on one GPU, PJ_CSR_CACHE ignored; a negative cycle is an error and no
+// sol_file is written).
 //
 // Multi-source (Johnson-style rows; no reference counterpart, the reference
 // takes one source per run, :448): PJ_SOURCES = a list of sources separated by
@@ -246,7 +250,46 @@ void write_tree(pj_graph* g, int source, int64_t n, const char* path) {
     std::cerr << "the parent tree has been saved in file " << path << std::endl;
 }
 
-int run_single(const char* webfile, int source, const char* out, int weighted) {
+// the signed load of PJ_SIGNED=1 (no CSR cache: the format carries no potentials)
+pj_graph* load_signed(pj_ctx* ctx, const char* webfile) {
+    pj_graph* g = nullptr;
+    pj_potential_stats ps{};
+    const int rc = pj_load_snap_signed(ctx, webfile, &ps, &g);
+    if (rc != PJ_OK) fail("pj_load_snap_signed", rc);
+    std::cerr << "potentials: " << ps.negative_edges << " negative weights, " << ps.rounds
+              << " Bellman-Ford rounds, min potential " << ps.min_potential << std::endl;
+    return g;
+}
+
+// PJ_SIGNED=1 with PJ_SOURCES: the weighted batch on one GPU, one sol_file per source
+int run_signed_sources(const char* webfile, const std::vector<int64_t>& sources, const char* pattern) {
+    pj_ctx* ctx = nullptr;
+    int rc = pj_create(env_int("PJ_DEVICE", env_int("LOCAL_RANK", 0)), &ctx);
+    if (rc != PJ_OK) fail("pj_create", rc);
+    pj_graph* g = load_signed(ctx, webfile);
+    int64_t n = 0;
+    pj_graph_info(g, &n, nullptr, nullptr, nullptr);
+    std::cerr << "N = " << n << std::endl;
+    print_msg("read in the webgraph is done.");
+    std::cerr << "compute shortest paths from " << sources.size() << " source nodes" << std::endl;
+    print_msg("parallel Johnson's algorithm starts......");
+    std::vector<std::string> paths;
+    std::vector<const char*> pp;
+    for (size_t i = 0; i < sources.size(); ++i) paths.push_back(sol_path(pattern, sources[i], i));
+    for (auto& q : paths) pp.push_back(q.c_str());
+    rc = pj_sssp_batch_write(g, sources.data(), (int)sources.size(), pp.data(), 0);
+    if (rc != PJ_OK) fail("pj_sssp_batch_write", rc);
+    pj_stats st{};
+    pj_last_stats(g, &st);
+    print_msg("parallel Johnson's algorithm completes.");
+    std::cout << "Time: " << st.kernel_ms / 1000.0 << " seconds when using " << 1 << " processes." << std::endl;
+    std::cerr << "the shortest path distance vectors have been saved in files " << pattern << std::endl;
+    pj_graph_destroy(g);
+    pj_destroy(ctx);
+    return 0;
+}
+
+int run_single(const char* webfile, int source, const char* out, int weighted, int is_signed = 0) {
     Phases ph;
     pj_ctx* ctx = nullptr;
     int rc = pj_create(env_int("PJ_DEVICE", env_int("LOCAL_RANK", 0)), &ctx);
@@ -254,8 +297,12 @@ int run_single(const char* webfile, int source, const char* out, int weighted) {
     ph.mark("init");
     pj_graph* g = nullptr;
     const std::string cache = cache_path(webfile);
-    rc = pj_load_snap_cached(ctx, webfile, weighted, cache.empty() ? nullptr : cache.c_str(), 1, &g);
-    if (rc != PJ_OK) fail("pj_load_snap", rc);
+    if (is_signed) {
+        g = load_signed(ctx, webfile);
+    } else {
+        rc = pj_load_snap_cached(ctx, webfile, weighted, cache.empty() ? nullptr : cache.c_str(), 1, &g);
+        if (rc != PJ_OK) fail("pj_load_snap", rc);
+    }
     int64_t n = 0;
     pj_graph_info(g, &n, nullptr, nullptr, nullptr);
     std::cerr << "N = " << n << std::endl;  // :320
@@ -323,7 +370,12 @@ int main(int argc, char* argv[]) {
     }
     if (rank != 0) return 0;
     const int P = process_count();
-    const int weighted = env_int("PJ_WEIGHTED", 0);
+    const int is_signed = env_int("PJ_SIGNED", 0) != 0;
+    const int weighted = is_signed ? 1 : env_int("PJ_WEIGHTED", 0);
+    if (is_signed && P > 1) {
+        std::cerr << "PJ_SIGNED: signed weights run on one GPU (P = 1); the partitions carry no potentials" << std::endl;
+        std::exit(-1);
+    }
 
     print_msg("process 0 reads in the web graph data......");
     const char* srcs = std::getenv("PJ_SOURCES");
@@ -333,8 +385,9 @@ int main(int argc, char* argv[]) {
                   << std::endl;
         std::exit(-1);
     }
+    if (srcs && *srcs && is_signed) return run_signed_sources(argv[1], parse_sources(srcs), argv[3]);
     if (srcs && *srcs) return run_multi_source(argv[1], parse_sources(srcs), argv[3], P, weighted);
     const int source_node = std::atoi(argv[2]);  // :448
     if (P > 1) return run_partitioned(argv[1], source_node, argv[3], P, weighted);
-    return run_single(argv[1], source_node, argv[3], weighted);
+    return run_single(argv[1], source_node, argv[3], weighted, is_signed);
 }

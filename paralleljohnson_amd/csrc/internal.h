@@ -286,6 +286,15 @@ struct Graph {
     i64 last_source = -1;      // source of the single-source result in dist (parent tree)
     bool batch_stats = false;  // stats describe the last pj_sssp_batch
     pj_load_stats load{};      // how the graph was built (pj_graph_load_stats)
+    // signed graphs (pj_load_*_signed, potential.hip): col / w / dist hold the REDUCED weights
+    // w' = w + h[u] - h[v] and distances d' (the tree and reach kernels read dist with w);
+    // dist_true is the row in true distances that pj_copy_dist / pj_dist_device serve
+    bool is_signed = false;
+    DevBuf<int32_t> h;          // potentials (n int32, <= 0)
+    DevBuf<int32_t> dist_true;  // the last single-source row, back-transformed (signed_result)
+    DevBuf<u64> true_cnt;       // device counter of the back-transform
+    bool true_valid = false;    // dist_true holds the last solve's row
+    i64 true_capped = 0;        // its vertices with d' < PJ_INT_INF <= d (reported unreached)
     pj_stats stats{};
 
     const void* row_ptr() const { return off64 ? (const void*)row64.p : (const void*)row32.p; }
@@ -320,12 +329,14 @@ struct ParseResult {
     double h2d_ms = 0, parse_ms = 0;
 };
 // Parses `len` bytes of host text on the device; fills device COO.
+// is_signed (with weighted): the third column may be negative (w holds int32 bit patterns) and a
+// missing one reads as 0
 ParseResult parse_snap_device(Ctx& ctx, const char* host_text, i64 len, bool weighted,
-                              DevBuf<u32>& src, DevBuf<u32>& dst, DevBuf<u32>& w);
+                              DevBuf<u32>& src, DevBuf<u32>& dst, DevBuf<u32>& w, bool is_signed = false);
 // The same from text already on the device (len bytes, zero-padded to padded_text_bytes(len)).
 i64 padded_text_bytes(i64 len);
 ParseResult parse_device_text(Ctx& ctx, const uint8_t* text, i64 len, bool weighted, DevBuf<u32>& src,
-                              DevBuf<u32>& dst, DevBuf<u32>& w);
+                              DevBuf<u32>& dst, DevBuf<u32>& w, bool is_signed = false);
 
 void generate_webgraph_device(Ctx& ctx, i64 n_ids, i64 n_edges, uint64_t seed, DevBuf<u32>& src,
                               DevBuf<u32>& dst);
@@ -352,7 +363,16 @@ void msbfs_solve(Graph& g, const int64_t* sources, int n_src, int32_t* dist_out)
 // index, sources in the pass, device rows [ns][n]) runs with the device idle.
 using MsPassFn = std::function<void(int, int, const int32_t*)>;
 void msbfs_each(Graph& g, const int64_t* sources, int n_src, const MsPassFn& on_pass);
-void reach_stats(Graph& g, i64* n_r, i64* m_r);
+void reach_stats(Graph& g, i64* n_r, i64* m_r, const int32_t* dist = nullptr);  // dist: default g.dist
+// signed weights (potential.hip): Bellman-Ford potentials h of the device COO (w = int32 bit
+// patterns), then w := w + h[src] - h[dst] in place. PJ_OK, PJ_ERR_NEGCYCLE or PJ_ERR_RANGE; st is
+// filled either way, w rewritten only on PJ_OK.
+int signed_potentials(Ctx& ctx, const u32* src, const u32* dst, u32* w, i64 nnz, i64 n, DevBuf<int32_t>& h,
+                      pj_potential_stats& st);
+// out[v] of a row solved on the reduced weights (pj.h output contract; in place when out == dred);
+// *capped (device, may be NULL) += the vertices with d' < PJ_INT_INF <= d
+void signed_correct(const int32_t* dred, const int32_t* h, i64 n, i64 source, int32_t* out, u64* capped,
+                    unsigned grid_cap, hipStream_t s);
 // shortest-path tree of g.dist (tree.hip)
 void parent_tree(Graph& g, i64 source, int64_t* host_out);
 void validate_tree(Graph& g, i64 source, const int64_t* host_parent, pj_tree_report* rep);

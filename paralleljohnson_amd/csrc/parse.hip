@@ -164,7 +164,8 @@ __device__ __forceinline__ int extract(T& t, int64_t len, int64_t& p, i64& out) 
 // One line: `src dst [w]` with the reference's `>> int` semantics (:92-93).
 // Returns false when the line is undefined behaviour for the reference.
 template <typename T>
-__device__ __forceinline__ bool parse_line(T& t, int64_t len, int64_t& p, bool weighted, i64& u, i64& v, i64& wt) {
+__device__ __forceinline__ bool parse_line(T& t, int64_t len, int64_t& p, bool weighted, bool sgn, i64& u, i64& v,
+                                           i64& wt) {
     u = 0;
     v = 0;
     wt = 1;
@@ -177,7 +178,9 @@ __device__ __forceinline__ bool parse_line(T& t, int64_t len, int64_t& p, bool w
             if (r == 0) wt = 0;  // stream failed: the weight extraction stores nothing -> 0
             else {
                 const int r3 = extract(t, len, p, wt);
-                bad = r3 < 0 || wt < 0;
+                if (!sgn) bad = r3 < 0 || wt < 0;
+                else if (r3 == -1) wt = 0;  // signed: a missing third field reads as 0
+                else bad = r3 < 0 || wt > 2147483647ll || wt < -2147483647ll;  // |w| fits int32
             }
         }
     }
@@ -200,7 +203,8 @@ __global__ __launch_bounds__(PB) void parse_count_k(const uint8_t* __restrict__ 
 // layout, LdsBytes) with coalesced 16-byte loads; every lane then parses the lines
 // that start in its 64-byte segment from LDS (byte loads from global were
 // stride-64 across the wave: one cache line per lane per byte).
-__global__ __launch_bounds__(PB) void parse_lines_k(const uint8_t* __restrict__ text, i64 len, int weighted,
+// (sgn: a third field with a sign fails the fast path's digit test and goes through parse_line)
+__global__ __launch_bounds__(PB) void parse_lines_k(const uint8_t* __restrict__ text, i64 len, int weighted, int sgn,
                                                     const u64* __restrict__ block_off, u32* __restrict__ src,
                                                     u32* __restrict__ dst, u32* __restrict__ w,
                                                     u32* __restrict__ bmax, u64* __restrict__ errpos) {
@@ -253,11 +257,11 @@ __global__ __launch_bounds__(PB) void parse_lines_k(const uint8_t* __restrict__ 
             wt = fc;
             ok = true;
         } else {
-            ok = parse_line(sb, wlen, q, weighted != 0, u, v, wt);
+            ok = parse_line(sb, wlen, q, weighted != 0, sgn != 0, u, v, wt);
             if (q >= wlen && base + wlen < len) {  // ran into the window end: slow path
                 int64_t pg = start;
                 const uint8_t* tg = text;
-                ok = parse_line(tg, len, pg, weighted != 0, u, v, wt);
+                ok = parse_line(tg, len, pg, weighted != 0, sgn != 0, u, v, wt);
             }
         }
         if (!ok) {
@@ -267,7 +271,7 @@ __global__ __launch_bounds__(PB) void parse_lines_k(const uint8_t* __restrict__ 
         }
         src[idx] = (u32)u;
         dst[idx] = (u32)v;
-        if (w) w[idx] = (u32)wt;
+        if (w) w[idx] = (u32)wt;  // (signed: the int32 bit pattern)
         ++idx;
         mx = u > mx ? u : mx;
         mx = v > mx ? v : mx;
@@ -305,7 +309,7 @@ __global__ __launch_bounds__(1024) void max_blocks_k(const u32* __restrict__ bma
 i64 padded_text_bytes(i64 len) { return (len + PCHUNK - 1) / PCHUNK * PCHUNK + PTAIL; }
 
 ParseResult parse_snap_device(Ctx& ctx, const char* host_text, i64 len, bool weighted, DevBuf<u32>& src,
-                              DevBuf<u32>& dst, DevBuf<u32>& w) {
+                              DevBuf<u32>& dst, DevBuf<u32>& w, bool is_signed) {
     hipStream_t s = ctx.stream;
     const auto t0 = std::chrono::steady_clock::now();
     const i64 padded = padded_text_bytes(len);
@@ -314,14 +318,14 @@ ParseResult parse_snap_device(Ctx& ctx, const char* host_text, i64 len, bool wei
     if (len) PJ_HIP(hipMemcpyAsync(text.p, host_text, (size_t)len, hipMemcpyHostToDevice, s));
     PJ_HIP(hipStreamSynchronize(s));
     const double h2d_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    ParseResult r = parse_device_text(ctx, text.p, len, weighted, src, dst, w);
+    ParseResult r = parse_device_text(ctx, text.p, len, weighted, src, dst, w, is_signed);
     r.h2d_ms = h2d_ms;
     return r;
 }
 
 // text: len bytes on the device, zero-padded to padded_text_bytes(len)
 ParseResult parse_device_text(Ctx& ctx, const uint8_t* text, i64 len, bool weighted, DevBuf<u32>& src,
-                              DevBuf<u32>& dst, DevBuf<u32>& w) {
+                              DevBuf<u32>& dst, DevBuf<u32>& w, bool is_signed) {
     hipStream_t s = ctx.stream;
     ParseResult r;
     const auto t1 = std::chrono::steady_clock::now();
@@ -344,7 +348,8 @@ ParseResult parse_device_text(Ctx& ctx, const uint8_t* text, i64 len, bool weigh
     dst.alloc((size_t)total);
     if (weighted) w.alloc((size_t)total);
     if (nblocks && total) {
-        parse_lines_k<<<(unsigned)nblocks, PB, 0, s>>>(text, len, weighted ? 1 : 0, boff.p, src.p, dst.p,
+        parse_lines_k<<<(unsigned)nblocks, PB, 0, s>>>(text, len, weighted ? 1 : 0, is_signed ? 1 : 0, boff.p,
+                                                      src.p, dst.p,
                                                       weighted ? w.p : nullptr, bcnt.p, scal.p + 1);
         PJ_LAUNCH_CHECK();
         max_blocks_k<<<1, 1024, 0, s>>>(bcnt.p, nblocks, scal.p);
