@@ -289,6 +289,36 @@ int pj_sssp_batch(pj_graph* g, const int64_t* sources, int n_src, int32_t* dist_
  * :615-620). Rows are copied to the host in groups and written by a pool of
  * host threads while the GPU computes the next pass. strict as pj_write_sol. */
 int pj_sssp_batch_write(pj_graph* g, const int64_t* sources, int n_src, const char* const* paths, int strict);
+/* pj_sssp_batch plus the predecessor rows: parent_out is n_src x n int32 (host), row i =
+ * what pj_sssp(g, sources[i]) followed by pj_parent_tree would give (the definition in the
+ * shortest-path tree section: smallest tight in-neighbour, the zero-weight hop rule,
+ * parent[source] = source, -1 where the reported distance is PJ_INT_INF; a source outside
+ * [0, n) gives a row of -1). dist_out and parent_out may each be NULL (parent_out == NULL is
+ * pj_sssp_batch). Parents are int32: a graph with more than INT32_MAX vertices is
+ * PJ_ERR_RANGE. The state afterwards is that of pj_sssp_batch (pj_copy_dist and
+ * pj_parent_tree return PJ_ERR_STATE, pj_last_stats describes the batch); kernel_ms stays
+ * the solves alone, the parent rows' device time is pj_last_parents_ms.
+ * Unit weights: a pass's parent block (64 W x n int32, like its distance block, allocated on
+ * the slot the first time parents are asked for and counted in the slot budget from then on)
+ * comes from the pass's level archive in one kernel (msbfs.hip ms_parents_k);
+ * where the archive does not hold the whole pass (more levels than archive entries, no
+ * archive), or a symmetric graph's id-sorted copy of its rows (4 bytes per entry, built on
+ * first use) does not fit in half the free device memory, the rows are computed one at a
+ * time like the weighted ones. Option batch_parents_path: 0 automatic, 1 always per row,
+ * 2 the archive wherever it covers the pass.
+ * Weighted graphs: one edge scan per row (tree.hip) on the stream of the row's solve.
+ * Signed graphs: the parents are taken in reduced space, as pj_parent_tree does, before
+ * the row is rewritten in true distances; if any row has a vertex with d' < PJ_INT_INF <= d
+ * the call returns PJ_ERR_RANGE after the batch (the last error names the first such
+ * source), mirroring pj_parent_tree.
+ * Refused on: the n-GPU handle (pj_multi_*) has no parent entry. */
+int pj_sssp_batch_parents(pj_graph* g, const int64_t* sources, int n_src, int32_t* dist_out, int32_t* parent_out);
+/* pj_sssp_batch_write plus one parent file per source: parent_paths[i] gets the bytes
+ * pj_write_parents would write for row i. parent_paths may be NULL (= pj_sssp_batch_write). */
+int pj_sssp_batch_write_parents(pj_graph* g, const int64_t* sources, int n_src, const char* const* sol_paths,
+                                const char* const* parent_paths, int strict);
+/* Device time (ms, HIP events) spent on the parent rows of the last batch; 0 when it had none. */
+int pj_last_parents_ms(const pj_graph* g, double* out);
 /* Statistics of the last solve. pj_reach_stats additionally computes
  * reached / reached_edges on the device (not part of kernel_ms). */
 int pj_last_stats(const pj_graph* g, pj_stats* out);

@@ -130,6 +130,9 @@ _SIGS = {
     "pj_host_unpin": ([_P], _INT),
     "pj_sssp_batch": ([_P, _P, _INT, _P], _INT),
     "pj_sssp_batch_write": ([_P, _P, _INT, _P, _INT], _INT),
+    "pj_sssp_batch_parents": ([_P, _P, _INT, _P, _P], _INT),
+    "pj_sssp_batch_write_parents": ([_P, _P, _INT, _P, _P, _INT], _INT),
+    "pj_last_parents_ms": ([_P, _P], _INT),
     "pj_device_count": ([_P], _INT),
     "pj_last_stats": ([_P, _P], _INT),
     "pj_reach_stats": ([_P, _P], _INT),
@@ -297,12 +300,45 @@ class Graph:
         _check(_lib.pj_sssp_batch(self._h, _ptr(src), len(src), _ptr(out)))
         return out[:, : self.n] if copy else None
 
-    def sssp_batch_write(self, sources: Sequence[int], paths: Sequence[str], strict: bool = True):
-        """Row i of the batch written as the sol_file paths[i] (pj_sssp_batch_write)."""
+    def sssp_batch_parents(self, sources: Sequence[int], out=None):
+        """(dist, parent): the batch's distance rows and their predecessor rows, both n_src x n
+        int32; parent[i] is what sssp(sources[i]) followed by parent_tree() gives (-1 = unreached,
+        parent[i][sources[i]] = sources[i]) (pj_sssp_batch_parents). out: a pair of C-contiguous
+        int32 arrays of shape (n_src, max(n, 1)) to fill instead of new ones (timed loops)."""
+        src = np.ascontiguousarray(np.asarray(sources, dtype=np.int64))
+        shape = (len(src), max(self.n, 1))
+        if out is not None:
+            dist, par = out
+            for a in (dist, par):
+                if a.dtype != np.int32 or a.shape != shape or not a.flags.c_contiguous:
+                    raise ValueError("sssp_batch_parents: out must be two contiguous int32 arrays of (n_src, max(n, 1))")
+        else:
+            dist = np.empty(shape, np.int32)
+            par = np.empty(shape, np.int32)
+        _check(_lib.pj_sssp_batch_parents(self._h, _ptr(src), len(src), _ptr(dist), _ptr(par)))
+        return dist[:, : self.n], par[:, : self.n]
+
+    def last_parents_ms(self) -> float:
+        """Device time (ms) of the last batch's parent rows; 0 when it had none (pj_last_parents_ms)."""
+        out = ctypes.c_double(0)
+        _check(_lib.pj_last_parents_ms(self._h, ctypes.byref(out)))
+        return out.value
+
+    def sssp_batch_write(self, sources: Sequence[int], paths: Sequence[str], strict: bool = True,
+                         parent_paths: Optional[Sequence[str]] = None):
+        """Row i of the batch written as the sol_file paths[i] (pj_sssp_batch_write); with parent_paths
+        also its parent row as parent_paths[i], the bytes of write_parents (pj_sssp_batch_write_parents)."""
         src = np.ascontiguousarray(np.asarray(sources, dtype=np.int64))
         if len(paths) != len(src):
             raise ValueError("one path per source")
         arr = (ctypes.c_char_p * max(len(paths), 1))(*[os.fsencode(p) for p in paths])
+        if parent_paths is not None:
+            if len(parent_paths) != len(src):
+                raise ValueError("one parent path per source")
+            parr = (ctypes.c_char_p * max(len(parent_paths), 1))(*[os.fsencode(p) for p in parent_paths])
+            _check(_lib.pj_sssp_batch_write_parents(self._h, _ptr(src), len(src), ctypes.cast(arr, ctypes.c_void_p),
+                                                    ctypes.cast(parr, ctypes.c_void_p), int(strict)))
+            return
         _check(_lib.pj_sssp_batch_write(self._h, _ptr(src), len(src), ctypes.cast(arr, ctypes.c_void_p),
                                         int(strict)))
 

@@ -272,11 +272,12 @@ int finish_graph(pj_ctx* ctx, std::unique_ptr<pj_graph>& pg, pj_graph** out) {
     return PJ_OK;
 }
 
-size_t format_rows(const int32_t* d, int64_t a, int64_t b, char* o) {
+// (inf: PJ_INT_INF prints as "inf", the sol_file form; parent files print every id as a number)
+size_t format_rows(const int32_t* d, int64_t a, int64_t b, char* o, bool inf = true) {
     size_t k = 0;
     for (int64_t i = a; i < b; ++i) {
         int32_t x = d[i];
-        if (x == PJ_INT_INF) {
+        if (inf && x == PJ_INT_INF) {
             o[k++] = 'i';
             o[k++] = 'n';
             o[k++] = 'f';
@@ -304,8 +305,9 @@ size_t format_rows(const int32_t* d, int64_t a, int64_t b, char* o) {
 // the bytes of pj_write_sol), overlapped with the next rows' GPU work.
 class BatchWriter {
   public:
-    BatchWriter(size_t n, const char* const* paths, bool strict, std::atomic<int>* err)
-        : n_(n), paths_in_(paths), strict_(strict), err_(err) {
+    // parents: the rows are parent rows, written with the bytes of pj_write_parents
+    BatchWriter(size_t n, const char* const* paths, bool strict, std::atomic<int>* err, bool parents = false)
+        : n_(n), paths_in_(paths), strict_(strict), parents_(parents), err_(err) {
         const size_t row_bytes = std::max<size_t>(4 * n, 4);
         group_ = (int)std::max<size_t>(1, std::min<size_t>(256, ((size_t)256 << 20) / row_bytes));
         for (auto& b : buf_) b.alloc(row_bytes / 4 * (size_t)group_);
@@ -335,7 +337,7 @@ class BatchWriter {
         const int slot = cur_, k = fill_;
         for (int t = 0; t < nthreads_ && t < k; ++t)
             th_[slot].emplace_back([this, slot, k, t] {
-                std::vector<char> out(n_ * 12 + 16);
+                std::vector<char> out(n_ * 12 + 32);
                 for (int r = t; r < k; r += nthreads_) write_one(buf_[slot].p + (size_t)r * n_, paths_[slot][r], out);
             });
         cur_ ^= 1;
@@ -347,10 +349,10 @@ class BatchWriter {
             if (strict_) fail(PJ_ERR_IO, "cannot open " + path);
             return;
         }
-        static const char hdr[] = "the vector is:\n";
-        size_t k = sizeof(hdr) - 1;
+        const char* hdr = parents_ ? "the parent tree is:\n" : "the vector is:\n";
+        size_t k = std::strlen(hdr);
         std::memcpy(out.data(), hdr, k);
-        k += format_rows(d, 0, (int64_t)n_, out.data() + k);
+        k += format_rows(d, 0, (int64_t)n_, out.data() + k, !parents_);
         const bool ok = std::fwrite(out.data(), 1, k, f) == k;
         if ((std::fclose(f) != 0 || !ok) && strict_) fail(PJ_ERR_IO, "write failed: " + path);
     }
@@ -372,7 +374,7 @@ class BatchWriter {
     }
     size_t n_;
     const char* const* paths_in_;
-    bool strict_;
+    bool strict_, parents_;
     std::atomic<int>* err_;
     int group_ = 1, nthreads_ = 1, cur_ = 0, fill_ = 0;
     PinnedBuf<int32_t> buf_[2];
@@ -999,6 +1001,7 @@ int pj_sssp_batch(pj_graph* pg, const int64_t* sources, int n_src, int32_t* dist
     return guarded([&] {
         Graph& g = pg->g;
         bind(*g.ctx);
+        g.parents_ms = 0;
         if (g.weighted) {
             delta_batch(g, sources, n_src, g.batch_streams, [&](int i, const int32_t* dev, hipStream_t s) {
                 if (dist_out && g.n) {
@@ -1025,6 +1028,7 @@ int pj_sssp_batch_write(pj_graph* pg, const int64_t* sources, int n_src, const c
         Graph& g = pg->g;
         bind(*g.ctx);
         const size_t n = (size_t)g.n;
+        g.parents_ms = 0;
         std::atomic<int> err{PJ_OK};
         BatchWriter wr(n, paths, strict != 0, &err);
         if (g.weighted) {
@@ -1048,6 +1052,137 @@ int pj_sssp_batch_write(pj_graph* pg, const int64_t* sources, int n_src, const c
         }
         return (int)PJ_OK;
     });
+}
+
+// ---- batch parents: the predecessor rows of a batch (tree.hip per row, msbfs.hip ms_parents_k) ----
+
+namespace {
+
+// The batch of pj_sssp_batch / pj_sssp_batch_write with the parent rows. Distances go to
+// dist_out and / or dw, parents to par_out and / or pw (each may be null).
+int batch_with_parents(Graph& g, const int64_t* sources, int n_src, int32_t* dist_out, int32_t* par_out,
+                       BatchWriter* dw, BatchWriter* pw, const char* who) {
+    if (g.n > (i64)INT32_MAX) {
+        set_error(std::string(who) + ": parent ids are int32, the graph has more than INT32_MAX vertices");
+        return (int)PJ_ERR_RANGE;
+    }
+    const size_t n = (size_t)g.n;
+    g.parents_ms = 0;
+    double pms = 0;
+    if (g.weighted) {
+        // one row at a time, on the slot's stream, before a signed row is rewritten in true distances
+        ParentWs ws;
+        DevBuf<int32_t> prow(std::max<size_t>(n, 1));
+        DevBuf<u64> capped;  // signed: per row, the vertices with d' < PJ_INT_INF <= d
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        PJ_HIP(hipEventCreate(&e0));
+        PJ_HIP(hipEventCreate(&e1));
+        struct EvGuard {
+            hipEvent_t a, b;
+            ~EvGuard() {
+                (void)hipEventDestroy(a);
+                (void)hipEventDestroy(b);
+            }
+        } guard{e0, e1};
+        if (g.is_signed && n_src) {
+            capped.alloc((size_t)n_src);
+            PJ_HIP(hipMemsetAsync(capped.p, 0, sizeof(u64) * (size_t)n_src, g.ctx->stream));
+            PJ_HIP(hipStreamSynchronize(g.ctx->stream));
+        }
+        delta_batch(g, sources, n_src, g.batch_streams, [&](int i, const int32_t* dev, hipStream_t s) {
+            PJ_HIP(hipEventRecord(e0, s));
+            parent_row(g, dev, sources[i], prow.p, s, ws);
+            PJ_HIP(hipEventRecord(e1, s));
+            if (g.is_signed)
+                signed_correct(dev, g.h.p, g.n, sources[i], const_cast<int32_t*>(dev), capped.p + i,
+                               (unsigned)g.ctx->cu_count * 8u, s);
+            if (n) {
+                if (dist_out) PJ_HIP(hipMemcpyAsync(dist_out + (size_t)i * n, dev, 4 * n, hipMemcpyDeviceToHost, s));
+                if (par_out) PJ_HIP(hipMemcpyAsync(par_out + (size_t)i * n, prow.p, 4 * n, hipMemcpyDeviceToHost, s));
+            }
+            if (dw) dw->add_row(i, dev, s);
+            if (pw) pw->add_row(i, prow.p, s);
+            PJ_HIP(hipStreamSynchronize(s));  // (prow and ws serve the next row, on any slot's stream)
+            float ms = 0.f;
+            PJ_HIP(hipEventElapsedTime(&ms, e0, e1));
+            pms += ms;
+        });
+        if (g.is_signed && n_src) {
+            std::vector<u64> hc((size_t)n_src);
+            PJ_HIP(hipMemcpy(hc.data(), capped.p, sizeof(u64) * (size_t)n_src, hipMemcpyDeviceToHost));
+            for (int i = 0; i < n_src; ++i)
+                if (hc[(size_t)i]) {
+                    g.have_result = false;
+                    g.batch_stats = true;
+                    g.parents_ms = pms;
+                    set_error(std::string(who) + ": source " + std::to_string(sources[i]) + " (row " + std::to_string(i) +
+                              "): " + std::to_string(hc[(size_t)i]) +
+                              " vertices are reached on the reduced weights but their distance is >= PJ_INT_INF");
+                    return (int)PJ_ERR_RANGE;
+                }
+        }
+    } else {
+        msbfs_each_parents(g, sources, n_src, [&](int off, int ns, const int32_t* rows, const int32_t* par) {
+            if (n) {
+                if (dist_out)
+                    PJ_HIP(hipMemcpy(dist_out + (size_t)off * n, rows, 4 * (size_t)ns * n, hipMemcpyDeviceToHost));
+                if (par_out)
+                    PJ_HIP(hipMemcpy(par_out + (size_t)off * n, par, 4 * (size_t)ns * n, hipMemcpyDeviceToHost));
+            }
+            for (int k = 0; k < ns; ++k) {
+                if (dw) dw->add_row(off + k, rows + (size_t)k * n);
+                if (pw) pw->add_row(off + k, par + (size_t)k * n);
+            }
+        }, &pms);
+    }
+    g.parents_ms = pms;
+    g.have_result = false;  // g.dist does not hold a batch row
+    g.batch_stats = true;
+    return (int)PJ_OK;
+}
+
+}  // namespace
+
+int pj_sssp_batch_parents(pj_graph* pg, const int64_t* sources, int n_src, int32_t* dist_out, int32_t* parent_out) {
+    if (!pg || (n_src > 0 && !sources) || n_src < 0) return arg_error("pj_sssp_batch_parents: bad argument");
+    if (!parent_out) return pj_sssp_batch(pg, sources, n_src, dist_out);
+    return guarded([&] {
+        Graph& g = pg->g;
+        bind(*g.ctx);
+        return batch_with_parents(g, sources, n_src, dist_out, parent_out, nullptr, nullptr, "pj_sssp_batch_parents");
+    });
+}
+
+int pj_sssp_batch_write_parents(pj_graph* pg, const int64_t* sources, int n_src, const char* const* sol_paths,
+                                const char* const* parent_paths, int strict) {
+    if (!pg || (n_src > 0 && (!sources || !sol_paths)) || n_src < 0)
+        return arg_error("pj_sssp_batch_write_parents: bad argument");
+    if (!parent_paths) return pj_sssp_batch_write(pg, sources, n_src, sol_paths, strict);
+    for (int i = 0; i < n_src; ++i)
+        if (!sol_paths[i] || !parent_paths[i]) return arg_error("pj_sssp_batch_write_parents: a path is NULL");
+    return guarded([&] {
+        Graph& g = pg->g;
+        bind(*g.ctx);
+        std::atomic<int> err{PJ_OK};
+        BatchWriter dw((size_t)g.n, sol_paths, strict != 0, &err);
+        BatchWriter pw((size_t)g.n, parent_paths, strict != 0, &err, true);
+        const int rc = batch_with_parents(g, sources, n_src, nullptr, nullptr, &dw, &pw, "pj_sssp_batch_write_parents");
+        dw.finish();
+        pw.finish();
+        if (rc != PJ_OK) return rc;
+        if (err.load() != PJ_OK) {
+            const std::string m = dw.error();
+            set_error(m.empty() ? pw.error() : m);
+            return err.load();
+        }
+        return (int)PJ_OK;
+    });
+}
+
+int pj_last_parents_ms(const pj_graph* pg, double* out) {
+    if (!pg || !out) return arg_error("pj_last_parents_ms: bad argument");
+    *out = pg->g.parents_ms;
+    return PJ_OK;
 }
 
 int pj_last_stats(const pj_graph* pg, pj_stats* out) {
@@ -1120,6 +1255,7 @@ int pj_set_option(pj_graph* pg, const char* key, double value) {
         g.ms_width = (int)value;
     else if (k == "ms_alpha" && value >= 0) g.ms_alpha = value;
     else if (k == "ms_streams" && value >= 1 && value <= 4) g.ms_streams = (int)value;
+    else if (k == "batch_parents_path" && (value == 0 || value == 1 || value == 2)) g.batch_parents_path = (int)value;
     else return arg_error("pj_set_option: unknown key or bad value");
     return PJ_OK;
 }

@@ -27,6 +27,10 @@
 // PJ_SOURCES on one GPU, PJ_CSR_CACHE ignored; a negative cycle is an error and no
 // sol_file is written).
 //
+// PJ_PARENTS=<path> (P = 1): the parent tree of the solve. With PJ_SOURCES it is a pattern
+// like argv[3] ("{s}" / "{i}"; required with more than one source) and every source gets a
+// parent file; that form is not validated on the device.
+//
 // Multi-source (Johnson-style rows; no reference counterpart, the reference
 // takes one source per run, :448): PJ_SOURCES = a list of sources separated by
 // commas or blanks, or "@file" with one source per line (each read with atoi,
@@ -289,6 +293,56 @@ int run_signed_sources(const char* webfile, const std::vector<int64_t>& sources,
     return 0;
 }
 
+// PJ_SOURCES with PJ_PARENTS=<pattern> (P = 1): the batch on one GPU, one sol_file and one
+// parent file per source ("{s}" / "{i}" in the pattern as in argv[3]). The parent files are
+// not validated on the device: pj_validate_tree checks a single-source solve.
+int run_sources_parents(const char* webfile, const std::vector<int64_t>& sources, const char* pattern,
+                        const char* ppattern, int weighted, int is_signed) {
+    const std::string pp(ppattern);
+    if (sources.size() > 1 && pp.find("{s}") == std::string::npos && pp.find("{i}") == std::string::npos) {
+        std::cerr << "PJ_PARENTS: with more than one source the pattern needs {s} or {i} (the files would overwrite "
+                     "each other)" << std::endl;
+        std::exit(-1);
+    }
+    pj_ctx* ctx = nullptr;
+    int rc = pj_create(env_int("PJ_DEVICE", env_int("LOCAL_RANK", 0)), &ctx);
+    if (rc != PJ_OK) fail("pj_create", rc);
+    pj_graph* g = nullptr;
+    if (is_signed) {
+        g = load_signed(ctx, webfile);
+    } else {
+        const std::string cache = cache_path(webfile);
+        rc = pj_load_snap_cached(ctx, webfile, weighted, cache.empty() ? nullptr : cache.c_str(), 1, &g);
+        if (rc != PJ_OK) fail("pj_load_snap", rc);
+    }
+    int64_t n = 0;
+    pj_graph_info(g, &n, nullptr, nullptr, nullptr);
+    std::cerr << "N = " << n << std::endl;
+    print_msg("read in the webgraph is done.");
+    std::cerr << "compute shortest paths from " << sources.size() << " source nodes" << std::endl;
+    print_msg("parallel Johnson's algorithm starts......");
+    std::vector<std::string> paths, ppaths;
+    std::vector<const char*> sp, qp;
+    for (size_t i = 0; i < sources.size(); ++i) {
+        paths.push_back(sol_path(pattern, sources[i], i));
+        ppaths.push_back(sol_path(pp, sources[i], i));
+    }
+    for (auto& q : paths) sp.push_back(q.c_str());
+    for (auto& q : ppaths) qp.push_back(q.c_str());
+    rc = pj_sssp_batch_write_parents(g, sources.data(), (int)sources.size(), sp.data(), qp.data(), 0);
+    if (rc != PJ_OK) fail("pj_sssp_batch_write_parents", rc);
+    pj_stats st{};
+    pj_last_stats(g, &st);
+    print_msg("parallel Johnson's algorithm completes.");
+    std::cout << "Time: " << st.kernel_ms / 1000.0 << " seconds when using " << 1 << " processes." << std::endl;
+    std::cerr << "the shortest path distance vectors have been saved in files " << pattern << std::endl;
+    std::cerr << "the parent trees have been saved in files " << ppattern
+              << " (not validated on the device: the Graph500 checks need a single-source solve)" << std::endl;
+    pj_graph_destroy(g);
+    pj_destroy(ctx);
+    return 0;
+}
+
 int run_single(const char* webfile, int source, const char* out, int weighted, int is_signed = 0) {
     Phases ph;
     pj_ctx* ctx = nullptr;
@@ -380,11 +434,13 @@ int main(int argc, char* argv[]) {
     print_msg("process 0 reads in the web graph data......");
     const char* srcs = std::getenv("PJ_SOURCES");
     const char* parents = std::getenv("PJ_PARENTS");
-    if (parents && *parents && (P > 1 || (srcs && *srcs))) {
+    if (parents && *parents && P > 1) {
         std::cerr << "PJ_PARENTS: the parent tree needs a single-source run on one GPU (P = 1, no PJ_SOURCES)"
                   << std::endl;
         std::exit(-1);
     }
+    if (parents && *parents && srcs && *srcs)
+        return run_sources_parents(argv[1], parse_sources(srcs), argv[3], parents, weighted, is_signed);
     if (srcs && *srcs && is_signed) return run_signed_sources(argv[1], parse_sources(srcs), argv[3]);
     if (srcs && *srcs) return run_multi_source(argv[1], parse_sources(srcs), argv[3], P, weighted);
     const int source_node = std::atoi(argv[2]);  // :448

@@ -196,6 +196,8 @@ struct Graph {
     DevBuf<u32> col, ccol;  // ccol/crow*: CSC (in-edges) for pull steps; alias CSR when symmetric
     DevBuf<u32> w;          // CSR-aligned weights (weighted graphs)
     DevBuf<u32> ccol_hf;    // hub_first: the in-rows ordered highest-degree in-neighbour first (pull_ccol)
+    DevBuf<u32> ccol_asc;   // symmetric graphs: the rows in ascending id order (asc_ccol, batch parents)
+    int ccol_asc_state = 0; // 0 not tried yet, 1 built, -1 no room for it (the batch parents run per row)
 
     // per-solve workspace (lazily sized)
     DevBuf<int32_t> dist;
@@ -277,6 +279,8 @@ struct Graph {
                          // (1024 sources) 3% slower than 8)
     int ms_streams = 2;      // batch BFS: passes in flight at once (one stream + host thread each)
     double ms_alpha = 16.0;  // batch BFS: push levels while the frontier's out-edges < nnz / ms_alpha
+    int batch_parents_path = 0;  // batch parents on unit weights: 0 auto (= 2), 1 one edge scan per row (tree.hip),
+                                 // 2 from the level archive wherever it covers the pass (msbfs.hip ms_parents_k)
 
     bool have_result = false;
     // weighted: the last solve's distances are still in the solver's ids (R.dist); the first
@@ -285,6 +289,7 @@ struct Graph {
     i64 pending_source = -1;   // (a source without edges: its 0 is written after the gather)
     i64 last_source = -1;      // source of the single-source result in dist (parent tree)
     bool batch_stats = false;  // stats describe the last pj_sssp_batch
+    double parents_ms = 0;     // device time of the last batch's parent rows (pj_last_parents_ms)
     pj_load_stats load{};      // how the graph was built (pj_graph_load_stats)
     // signed graphs (pj_load_*_signed, potential.hip): col / w / dist hold the REDUCED weights
     // w' = w + h[u] - h[v] and distances d' (the tree and reach kernels read dist with w);
@@ -363,6 +368,12 @@ void msbfs_solve(Graph& g, const int64_t* sources, int n_src, int32_t* dist_out)
 // index, sources in the pass, device rows [ns][n]) runs with the device idle.
 using MsPassFn = std::function<void(int, int, const int32_t*)>;
 void msbfs_each(Graph& g, const int64_t* sources, int n_src, const MsPassFn& on_pass);
+// The same with the passes' parent rows (device, [ns][n] int32, laid out like the distance
+// rows): from the level archive or, where it does not cover the pass, row by row (tree.hip).
+// *parents_ms += their device time; the batch's kernel_ms stays that of the solves.
+using MsParentPassFn = std::function<void(int, int, const int32_t*, const int32_t*)>;
+void msbfs_each_parents(Graph& g, const int64_t* sources, int n_src, const MsParentPassFn& on_pass,
+                        double* parents_ms);
 void reach_stats(Graph& g, i64* n_r, i64* m_r, const int32_t* dist = nullptr);  // dist: default g.dist
 // signed weights (potential.hip): Bellman-Ford potentials h of the device COO (w = int32 bit
 // patterns), then w := w + h[src] - h[dst] in place. PJ_OK, PJ_ERR_NEGCYCLE or PJ_ERR_RANGE; st is
@@ -375,6 +386,15 @@ void signed_correct(const int32_t* dred, const int32_t* h, i64 n, i64 source, in
                     unsigned grid_cap, hipStream_t s);
 // shortest-path tree of g.dist (tree.hip)
 void parent_tree(Graph& g, i64 source, int64_t* host_out);
+// Scratch of parent_row: one per stream in use (the zero-weight phase's flags and hop depths).
+struct ParentWs {
+    DevBuf<u32> flag, hop;
+    PinnedBuf<u32> hflag;
+};
+// The same tree for any distance row of g in input ids (device, n int32), as n int32 in out
+// (device; -1 = no parent), enqueued on s; n <= INT32_MAX. On a weighted graph the host waits
+// on s once per 8 zero-weight levels.
+void parent_row(Graph& g, const int32_t* dist, i64 source, int32_t* out, hipStream_t s, ParentWs& ws);
 void validate_tree(Graph& g, i64 source, const int64_t* host_parent, pj_tree_report* rep);
 void debug_bitmaps(Graph& g, u64* vis0, u64* vis1, u64* fnew);
 

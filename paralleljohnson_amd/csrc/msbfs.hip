@@ -22,6 +22,12 @@
 // batch (profiles/r05/ms_dist_r5k.txt). A pass deeper than the archive expands it when it
 // fills and stores the later levels' distances directly, as before.
 //
+// Parent rows (pj_sssp_batch_parents): the archive also says who can be a parent:
+// u is a tight in-neighbour of v for source i exactly when entry a - 1 holds bit i at u and
+// entry a holds it at v. ms_parents_k reads the 64 W x n int32 parent block off the intact
+// archive after the expansion, full-line stores again; a pass the archive does not hold whole
+// (deeper than it, or no archive) takes tree.hip's edge scan per row on the distance block.
+//
 // Work mapping: one wave per 64 consecutive vertices; each lane walks its first
 // MS_SERIAL in-edges in a wave-uniform loop (predicated body), then the whole wave
 // scans the rest of long rows (web-graph in-hubs) 64 edges at a time. The masks
@@ -580,6 +586,196 @@ __global__ __launch_bounds__(MB) void ms_expand_k(i64 n, const u64* __restrict__
     }
 }
 
+// The parent block from the level archive: par[i][v] = the smallest in-neighbour u
+// of v with dist_i[u] + 1 == dist_i[v], i.e. with source bit i in entry a - 1 where v has it in
+// entry a; v itself in entry 0 (a source), -1 where no entry holds the bit. ccol must hold the
+// in-rows in ascending id order: the first hit of a scan is then the parent, the scan ends once
+// every source that arrived at that level is parented, and every pair is written once.
+// A wave takes 64 consecutive vertices and one mask word (64 sources) at a time: the parents go
+// to a 64 x 64 tile in LDS ([source bit][vertex]: a lane's writes stay on its own bank) and leave
+// it source by source as 64 consecutive int32, full-line streaming stores like ms_expand_k's
+// (stored on arrival they would be the masked partial-line writes that cost 8 of 11.5 ms per
+// batch in round 5). The NW = min(W, 8) waves of a workgroup take the same 64 vertices and
+// different mask words (wave w the words w, w + NW, ...): they walk the same in-rows and probe
+// the same mask rows (the words of a row share a line) at about the same time. (Measured equal
+// to one wave per 64 vertices taking the words in turn, 24.5 against 22.8-26.5 ms on MS1024:
+// the scans are bound by their chains of dependent loads, not by the lines fetched.) The waves
+// share nothing else: no barrier between them. Only written state is read: entry a's row of v
+// where entry a's bitmap holds v, entry a - 1's row of u where that entry's bitmap holds u,
+// entries below nlev.
+// The first MS_SERIAL in-edges of a row are scanned by its lane, the rest of a long row by the
+// whole wave, 64 ascending entries at a time: for a source bit the lowest lane with a hit holds
+// the smallest u.
+template <int W>
+constexpr int ms_parent_waves() { return W < 8 ? W : 8; }  // 16 KB of tile each: 8-10 waves per CU by LDS
+template <typename Off, int W>
+__global__ __launch_bounds__(64 * ms_parent_waves<W>()) void ms_parents_k(
+    i64 n, const Off* __restrict__ crow, const u32* __restrict__ ccol, const u64* __restrict__ arch,
+    const u64* __restrict__ zarch, i64 nzw, int nlev, int ns, int32_t* __restrict__ par) {
+    constexpr int NW = ms_parent_waves<W>();
+    __shared__ int32_t tiles[NW][64 * 64];
+    int32_t* tile = tiles[wave_id()];
+    const int lane = lane_id();
+    for (i64 base = (i64)blockIdx.x * 64; base < n; base += (i64)gridDim.x * 64) {
+        const i64 v = base + lane;
+        const bool inr = v < n;
+        u32 zm = 0;  // the entries holding a row for v
+        if (inr)
+            for (int a = 0; a < nlev; ++a)
+                if ((zarch[(i64)a * nzw + (base >> 6)] >> lane) & 1ull) zm |= 1u << a;
+        Off rb = 0, re = 0;
+        if (zm >> 1) {
+            rb = crow[v];
+            re = crow[v + 1];
+        }
+        const Off lim = (re - rb > (Off)MS_SERIAL) ? rb + (Off)MS_SERIAL : re;
+        for (int j = wave_id(); j < W && 64 * j < ns; j += NW) {
+            for (int b = 0; b < 64; ++b) tile[b * 64 + lane] = -1;
+            if (zm & 1u)  // v is a source
+                for (u64 m = arch[v * W + j]; m; m &= m - 1) tile[(__ffsll((long long)m) - 1) * 64 + lane] = (int32_t)v;
+            // Every lane walks its own levels (the entries a >= 1 of zm, ascending) and, inside a
+            // level, its own in-row: a step of the wave is one group of MS_U probes for every lane
+            // that still has a source to parent, whatever its level (level by level for the whole
+            // wave, the 64 vertices' levels add up: most steps had a few lanes at work).
+            u32 rem = zm & ~1u;  // levels not begun
+            int a = 0;           // the level at work
+            u64 need = 0;        // its sources not parented yet (arrived at v at level a)
+            Off k = rb;
+            auto next_level = [&]() {
+                while (need == 0 && rem) {
+                    a = __ffs((int)rem) - 1;
+                    rem &= rem - 1;
+                    need = arch[((i64)a * n + v) * W + j];
+                    k = rb;
+                }
+            };
+            next_level();
+            while (__ballot(need != 0)) {
+                // lanes past the serial part of a long row: the whole wave walks the rest
+                u64 open = __ballot(need != 0 && k >= lim);
+                while (open) {
+                    const int l = __ffsll((long long)open) - 1;
+                    open &= open - 1;
+                    const int al = __shfl(a, l, 64);
+                    const u64* __restrict__ Ap = arch + (size_t)(al - 1) * (size_t)n * W;  // the level before
+                    const u64* __restrict__ Zp = zarch + (i64)(al - 1) * nzw;
+                    const Off kb = __shfl(k, l, 64), ke = __shfl(re, l, 64);
+                    u64 want = __shfl(need, l, 64);
+                    for (Off kk = kb; kk < ke && want; kk += WAVE) {
+                        const Off k0 = kk + (Off)lane;
+                        const u32 u0 = k0 < ke ? ccol[k0] : 0u;
+                        u64 x = 0;
+                        if (k0 < ke && zbit(Zp, u0)) x = Ap[(i64)u0 * W + j] & want;
+                        u64 got = wave_or(x);
+                        want &= ~got;
+                        for (; got; got &= got - 1) {
+                            const int bit = __ffsll((long long)got) - 1;
+                            const u64 m = __ballot((x >> bit) & 1ull);
+                            if (lane == __ffsll((long long)m) - 1) tile[bit * 64 + l] = (int32_t)u0;
+                        }
+                    }
+                    // (every arrival has a tight in-neighbour, so want is 0 here; the lane's
+                    // level ends either way, which also bounds the loop)
+                    if (lane == l) need = 0;
+                }
+                next_level();
+                if (need != 0 && k < lim) {
+                    // MS_U in-edges: their ids, then their masks, as independent loads; hits in row order
+                    const u64* __restrict__ Ap = arch + (size_t)(a - 1) * (size_t)n * W;
+                    const u64* __restrict__ Zp = zarch + (i64)(a - 1) * nzw;
+                    u32 u[MS_U];
+#pragma unroll
+                    for (int q = 0; q < MS_U; ++q) u[q] = (k + (Off)q < lim) ? ccol[k + q] : 0u;
+                    bool z[MS_U];
+#pragma unroll
+                    for (int q = 0; q < MS_U; ++q) z[q] = (k + (Off)q < lim) && zbit(Zp, u[q]);
+                    u64 f[MS_U];
+#pragma unroll
+                    for (int q = 0; q < MS_U; ++q) f[q] = z[q] ? Ap[(i64)u[q] * W + j] : 0ull;
+#pragma unroll
+                    for (int q = 0; q < MS_U; ++q) {
+                        u64 hit = f[q] & need;
+                        need &= ~hit;
+                        for (; hit; hit &= hit - 1) tile[(__ffsll((long long)hit) - 1) * 64 + lane] = (int32_t)u[q];
+                    }
+                    k = (lim - k > (Off)MS_U) ? k + (Off)MS_U : lim;
+                    if (need != 0 && k >= lim && lim == re) need = 0;  // (a short row is done: cannot happen, see above)
+                }
+                next_level();
+            }
+            // (the long rows' parents were written by other lanes of the wave)
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            const int nb = min(64, ns - 64 * j);
+            if (inr)
+                for (int b = 0; b < nb; ++b)
+                    __builtin_nontemporal_store(tile[b * 64 + lane], par + (i64)(64 * j + b) * n + v);
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+}
+
+// row id of every CSR entry (one thread per entry: the last row that starts at or before it)
+template <typename Off>
+__global__ void ms_row_ids_k(const Off* __restrict__ row, i64 n, i64 nnz, u32* __restrict__ out) {
+    for (i64 k = (i64)blockIdx.x * blockDim.x + threadIdx.x; k < nnz; k += (i64)gridDim.x * blockDim.x) {
+        i64 lo = 0, hi = n - 1;
+        while (lo < hi) {
+            const i64 mid = (lo + hi + 1) >> 1;
+            if ((i64)row[mid] <= k) lo = mid;
+            else hi = mid - 1;
+        }
+        out[k] = (u32)lo;
+    }
+}
+
+// The in-rows in ascending id order, which ms_parents_k needs, or null when there are none
+// (the batch parents then run per row). A graph that is not symmetric has them already: its
+// CSC is a stable sort of the row-major CSR by column (graph.hip). A symmetric graph uses
+// its out-rows, in file order: an id-sorted copy is built once, on first use (sorted by
+// column, then stably by row), if its four sort buffers (one of them stays, 4 nnz bytes)
+// and the sort's workspace fit in half the free device memory and can be allocated.
+static const u32* asc_ccol(Graph& g) {
+    if (!g.symmetric) return g.ccol.p;
+    if (g.ccol_asc_state == 0) {
+        g.ccol_asc_state = -1;
+        const size_t nnz = (size_t)g.nnz;
+        if (nnz == 0) {
+            g.ccol_asc_state = 1;
+            return g.col.p;
+        }
+        if (17.0 * (double)nnz + 1048576.0 > 0.5 * (double)dev_free_bytes()) return nullptr;
+        try {
+            hipStream_t s = g.ctx->stream;
+            DevBuf<u32> buf[4];
+            for (auto& b : buf) b.alloc(nnz);
+            PJ_HIP(hipMemcpyAsync(buf[0].p, g.col.p, 4 * nnz, hipMemcpyDeviceToDevice, s));
+            const unsigned grid = grid_for(g.nnz, 256, (unsigned)g.ctx->cu_count * 16u);
+            if (g.off64) ms_row_ids_k<u64><<<grid, 256, 0, s>>>(g.row64.p, g.n, g.nnz, buf[2].p);
+            else ms_row_ids_k<u32><<<grid, 256, 0, s>>>(g.row32.p, g.n, g.nnz, buf[2].p);
+            PJ_LAUNCH_CHECK();
+            int bits = 1;
+            while (bits < 32 && ((i64)1 << bits) < g.n) ++bits;
+            SortWs ws;
+            u32 *c1 = nullptr, *r1 = nullptr, *r2 = nullptr, *c2 = nullptr;
+            radix_sort_pairs<u32>(buf[0].p, buf[1].p, buf[2].p, buf[3].p, g.nnz, bits, ws, s, &c1, &r1);
+            u32* calt = c1 == buf[0].p ? buf[1].p : buf[0].p;
+            u32* ralt = r1 == buf[2].p ? buf[3].p : buf[2].p;
+            radix_sort_pairs<u32>(r1, ralt, c1, calt, g.nnz, bits, ws, s, &r2, &c2);
+            PJ_HIP(hipStreamSynchronize(s));
+            for (auto& b : buf)
+                if (b.p == c2) g.ccol_asc = std::move(b);
+            g.ccol_asc_state = 1;
+        } catch (const Error& e) {
+            if (e.code != PJ_ERR_OOM) throw;
+            (void)hipGetLastError();
+            return nullptr;
+        }
+    }
+    return g.ccol_asc_state == 1 ? (g.nnz ? g.ccol_asc.p : g.col.p) : nullptr;
+}
+
 // One pass in flight: its masks, distance block, control block, stream and events.
 // Slot 0 runs on the ctx stream; further slots (option ms_streams) own a stream, and
 // passes of one batch run on the slots at once, one host thread each: a pass is a chain
@@ -591,30 +787,36 @@ struct MsSlot {
     DevBuf<u64> zarch;  // (PJ_MS_FZ) each entry's nonzero-row bitmap, nzw words
     int lcap = 0;
     DevBuf<int32_t> dist;
+    DevBuf<int32_t> par;  // the parent block, like dist; allocated the first time parents are asked for
+    ParentWs pws;         // scratch of the per-row parents
     DevBuf<int64_t> src;
     DevBuf<MsCtl> ctl;
     int64_t* host = nullptr;
     int32_t last_levels = 0;  // level iterations the previous pass used: sizes the first batch
     hipStream_t s = nullptr;
     bool own_stream = false;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, pe0 = nullptr, pe1 = nullptr;  // (pe*: around the parent rows)
     ~MsSlot() {
         if (host) (void)hipHostFree(host);
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
+        if (pe0) (void)hipEventDestroy(pe0);
+        if (pe1) (void)hipEventDestroy(pe1);
         if (own_stream && s) (void)hipStreamDestroy(s);
     }
 };
 
 struct MsWork {
     int W = 0;  // words per vertex mask of the allocation
+    bool parents = false;  // the slots' budget counts a parent block (a batch has asked for parents)
     std::vector<std::unique_ptr<MsSlot>> slots;
 };
 
 void delete_ms_work(MsWork* p) { delete p; }
 
 template <typename Off, int W>
-static void ms_pass(Graph& g, MsSlot& w, const int64_t* sources, int ns, double* kernel_ms, i64* levels) {
+static void ms_pass(Graph& g, MsSlot& w, const int64_t* sources, int ns, double* kernel_ms, i64* levels,
+                    const u32* asc, double* parents_ms) {
     hipStream_t s = w.s;
     const i64 n = g.n;
     const Off* crow = static_cast<const Off*>(g.crow_ptr());
@@ -655,6 +857,7 @@ static void ms_pass(Graph& g, MsSlot& w, const int64_t* sources, int ns, double*
     int batch = w.last_levels > 0 ? w.last_levels : 16;
     int next = 2;
     int fa = 0, fb = 1;  // entries of F and Fn (direct mode: alternating)
+    int covered = 0;     // archive entries that hold the whole pass (0: it left archive mode or never was in it)
     for (;;) {
         for (int i = 0; i < batch && L < INT_INF; ++i, ++L) {
             if (archive) {
@@ -684,6 +887,7 @@ static void ms_pass(Graph& g, MsSlot& w, const int64_t* sources, int ns, double*
             const int nlev = any ? (int)done + 1 : 1;
             ms_expand_k<W><<<grid, MB, 0, s>>>(n, w.arch.p, w.zarch.p, nzw, nlev, ns, w.dist.p);
             PJ_LAUNCH_CHECK();
+            covered = nlev;
             break;
         }
         if (done >= 0 || L >= INT_INF || !any) break;
@@ -700,45 +904,68 @@ static void ms_pass(Graph& g, MsSlot& w, const int64_t* sources, int ns, double*
         next = next < 1024 ? next * 2 : next;
     }
     PJ_HIP(hipEventRecord(w.ev1, s));
+    if (parents_ms) {
+        // the parent rows, outside the solve's timed region: from the archive while it holds the
+        // whole pass, else (no archive, a pass deeper than it, option batch_parents_path 1, no
+        // ascending in-rows) one edge scan per row over the finished distance block
+        PJ_HIP(hipEventRecord(w.pe0, s));
+        if (covered > 0 && asc && g.batch_parents_path != 1) {
+            constexpr int NW = ms_parent_waves<W>();
+            ms_parents_k<Off, W><<<grid_for(n, 64, (unsigned)g.ctx->cu_count * (unsigned)(16 / NW)), 64 * NW, 0, s>>>(
+                n, crow, asc, w.arch.p, w.zarch.p, nzw, covered, ns, w.par.p);
+            PJ_LAUNCH_CHECK();
+        } else {
+            for (int k = 0; k < ns; ++k)
+                parent_row(g, w.dist.p + (size_t)k * (size_t)n, sources[k], w.par.p + (size_t)k * (size_t)n, s, w.pws);
+        }
+        PJ_HIP(hipEventRecord(w.pe1, s));
+    }
     PJ_HIP(hipEventSynchronize(w.ev1));
     float ms = 0.f;
     PJ_HIP(hipEventElapsedTime(&ms, w.ev0, w.ev1));
     *kernel_ms += ms;
+    if (parents_ms) {
+        PJ_HIP(hipEventSynchronize(w.pe1));
+        PJ_HIP(hipEventElapsedTime(&ms, w.pe0, w.pe1));
+        *parents_ms += ms;
+    }
     const i64 lv = (i64)*(volatile int64_t*)w.host;
     if (any && lv >= 0) w.last_levels = (int32_t)lv + 1;
     *levels = std::max<i64>(*levels, lv);
 }
 
 template <typename Off>
-static void ms_pass_w(int W, Graph& g, MsSlot& w, const int64_t* sources, int ns, double* kernel_ms, i64* levels) {
-    if (W == 16) ms_pass<Off, 16>(g, w, sources, ns, kernel_ms, levels);
-    else if (W == 8) ms_pass<Off, 8>(g, w, sources, ns, kernel_ms, levels);
-    else if (W == 4) ms_pass<Off, 4>(g, w, sources, ns, kernel_ms, levels);
-    else if (W == 2) ms_pass<Off, 2>(g, w, sources, ns, kernel_ms, levels);
-    else ms_pass<Off, 1>(g, w, sources, ns, kernel_ms, levels);
+static void ms_pass_w(int W, Graph& g, MsSlot& w, const int64_t* sources, int ns, double* kernel_ms, i64* levels,
+                      const u32* asc, double* parents_ms) {
+    if (W == 16) ms_pass<Off, 16>(g, w, sources, ns, kernel_ms, levels, asc, parents_ms);
+    else if (W == 8) ms_pass<Off, 8>(g, w, sources, ns, kernel_ms, levels, asc, parents_ms);
+    else if (W == 4) ms_pass<Off, 4>(g, w, sources, ns, kernel_ms, levels, asc, parents_ms);
+    else if (W == 2) ms_pass<Off, 2>(g, w, sources, ns, kernel_ms, levels, asc, parents_ms);
+    else ms_pass<Off, 1>(g, w, sources, ns, kernel_ms, levels, asc, parents_ms);
 }
 
 // Device bytes of one pass slot: the distance block (64 W x n int32), the masks V (W words
-// per vertex) and the level archive (lcap entries of W words per vertex and a row bitmap).
-static double ms_slot_bytes(i64 n, int W, int lcap) {
-    return (double)n * (64.0 * W * 4.0 + (1.0 + lcap) * W * 8.0) + lcap * ((double)n / 8.0 + 16.0);
+// per vertex) and the level archive (lcap entries of W words per vertex and a row bitmap);
+// once a batch has asked for parents, also the parent block (64 W x n int32).
+static double ms_slot_bytes(i64 n, int W, int lcap, bool parents) {
+    return (double)n * ((parents ? 2.0 : 1.0) * 64.0 * W * 4.0 + (1.0 + lcap) * W * 8.0) + lcap * ((double)n / 8.0 + 16.0);
 }
 // Archive entries of a slot: MS_LCAP, fewer when the slot would exceed MS_BUDGET / 2 (the
 // later levels of a deeper pass store their distances directly); 2 = no archive.
-static int ms_lcap(i64 n, int W);
+static int ms_lcap(i64 n, int W, bool parents);
 constexpr double MS_BUDGET = 16e9;  // device bytes all slots of a batch may hold
 // Pass width: the fewest words that hold the batch, at most MS_WMAX (g.ms_width
 // caps it), with one slot's buffers within the budget.
-static int ms_words(const Graph& g, int n_src) {
+static int ms_words(const Graph& g, int n_src, bool parents) {
     int W = 1;
     const int cap = g.ms_width > 0 ? std::min(g.ms_width, MS_WMAX) : MS_WDEF;
-    while (W < cap && 64 * W < n_src && ms_slot_bytes(g.n, 2 * W, 2) <= MS_BUDGET) W *= 2;
+    while (W < cap && 64 * W < n_src && ms_slot_bytes(g.n, 2 * W, 2, parents) <= MS_BUDGET) W *= 2;
     return W;
 }
-static int ms_lcap(i64 n, int W) {
+static int ms_lcap(i64 n, int W, bool parents) {
     if (!PJ_MS_FZ) return 2;  // (the archive needs the row bitmaps)
     int lc = MS_LCAP;
-    while (lc > 2 && ms_slot_bytes(n, W, lc) > MS_BUDGET / 2) --lc;
+    while (lc > 2 && ms_slot_bytes(n, W, lc, parents) > MS_BUDGET / 2) --lc;
     return lc;
 }
 
@@ -760,23 +987,44 @@ static void ms_slot_alloc(Graph& g, MsSlot& sl, int W, int lcap, bool own_stream
     }
 }
 
-void msbfs_each(Graph& g, const int64_t* sources, int n_src, const MsPassFn& on_pass) {
+// the parent block and the per-row scratch of a slot (parents asked for; allocated on the caller's thread)
+static void ms_slot_parents(Graph& g, MsSlot& sl, int W) {
+    const size_t n = (size_t)g.n;
+    if (!sl.par.p) sl.par.alloc(n ? 64 * W * n : 1);
+    sl.pws.flag.ensure(4);
+    if (!sl.pws.hflag.p) sl.pws.hflag.alloc(1);
+    if (!sl.pe0) PJ_HIP(hipEventCreate(&sl.pe0));
+    if (!sl.pe1) PJ_HIP(hipEventCreate(&sl.pe1));
+}
+
+static void ms_run(Graph& g, const int64_t* sources, int n_src, const MsParentPassFn& on_pass, bool parents,
+                   double* parents_ms) {
     (void)pull_ccol(g);  // (built here, once, before the slots' host threads read it)
-    const int W = ms_words(g, n_src);
+    const u32* asc = parents && g.batch_parents_path != 1 ? asc_ccol(g) : nullptr;
+    const int W = ms_words(g, n_src, parents || (g.ms_work && g.ms_work->parents));
     const int per = 64 * W;
     const int npass = (n_src + per - 1) / per;
     int nslots = std::max(1, std::min(g.ms_streams, npass));
-    if (!g.ms_work || g.ms_work->W < W) {
+    bool fresh = !g.ms_work || g.ms_work->W < W;
+    // the first batch with parents: the parent block counts in the budget from now on, and
+    // slots whose archive would then be smaller are built anew
+    if (!fresh && parents && !g.ms_work->parents && !g.ms_work->slots.empty() &&
+        ms_lcap(g.n, g.ms_work->W, true) != g.ms_work->slots[0]->lcap)
+        fresh = true;
+    if (fresh) {
+        const bool had = g.ms_work && g.ms_work->parents;
         g.ms_work.reset(new MsWork());
         g.ms_work->W = W;
+        g.ms_work->parents = had;
     }
     MsWork& mw = *g.ms_work;
+    mw.parents = mw.parents || parents;
     // Every slot holds a whole pass (ms_slot_bytes: ~3.8 GB at n = 916K, W = 8, with a
     // 32-entry archive): the slots in flight stay within MS_BUDGET, and a slot beyond the
     // first is only added while it takes at most half the free device memory; if its
     // allocation still fails, the batch runs on the slots it has.
-    const int lcap = ms_lcap(g.n, mw.W);
-    const double sb = ms_slot_bytes(g.n, mw.W, lcap);
+    const int lcap = ms_lcap(g.n, mw.W, mw.parents);
+    const double sb = ms_slot_bytes(g.n, mw.W, lcap, mw.parents);
     while (nslots > 1 && (double)nslots * sb > MS_BUDGET) --nslots;
     if (mw.slots.empty()) {
         std::unique_ptr<MsSlot> sl(new MsSlot());
@@ -796,21 +1044,36 @@ void msbfs_each(Graph& g, const int64_t* sources, int n_src, const MsPassFn& on_
         mw.slots.push_back(std::move(sl));
     }
     nslots = std::min(nslots, (int)mw.slots.size());
+    if (parents) {
+        // slot 0 must hold a parent block; a further slot that cannot get one (half-of-free
+        // rule, or the allocation fails) is left out of this batch
+        ms_slot_parents(g, *mw.slots[0], mw.W);
+        for (int k = 1; k < nslots; ++k) {
+            MsSlot& sl = *mw.slots[(size_t)k];
+            try {
+                if (!sl.par.p && 256.0 * mw.W * (double)g.n > 0.5 * (double)dev_free_bytes()) throw Error(PJ_ERR_OOM, "");
+                ms_slot_parents(g, sl, mw.W);
+            } catch (const Error&) {
+                (void)hipGetLastError();
+                nslots = k;
+            }
+        }
+    }
     mw.slots[0]->s = g.ctx->stream;  // (pj_set_stream may change it)
     auto t0 = std::chrono::steady_clock::now();
     pj_stats st{};
-    double kms = 0;
+    double kms = 0, pms = 0;
     i64 levels = 0;
-    auto run = [&](MsSlot& sl, int off, double* k, i64* lv) {
+    auto run = [&](MsSlot& sl, int off, double* k, i64* lv, double* pm) {
         const int ns = std::min(per, n_src - off);
-        if (g.off64) ms_pass_w<u64>(W, g, sl, sources + off, ns, k, lv);
-        else ms_pass_w<u32>(W, g, sl, sources + off, ns, k, lv);
+        if (g.off64) ms_pass_w<u64>(W, g, sl, sources + off, ns, k, lv, asc, parents ? pm : nullptr);
+        else ms_pass_w<u32>(W, g, sl, sources + off, ns, k, lv, asc, parents ? pm : nullptr);
         return ns;
     };
     if (nslots == 1) {
         for (int off = 0; off < n_src; off += per) {
-            const int ns = run(*mw.slots[0], off, &kms, &levels);
-            if (on_pass) on_pass(off, ns, mw.slots[0]->dist.p);
+            const int ns = run(*mw.slots[0], off, &kms, &levels, &pms);
+            if (on_pass) on_pass(off, ns, mw.slots[0]->dist.p, parents ? mw.slots[0]->par.p : nullptr);
         }
     } else {
         PJ_HIP(hipStreamSynchronize(g.ctx->stream));
@@ -822,14 +1085,15 @@ void msbfs_each(Graph& g, const int64_t* sources, int n_src, const MsPassFn& on_
                 PJ_HIP(hipSetDevice(g.ctx->device));
                 MsSlot& sl = *mw.slots[(size_t)k];
                 for (int p; (p = next.fetch_add(1)) < npass;) {
-                    double km = 0;
+                    double km = 0, pm = 0;
                     i64 lv = 0;
                     const int off = p * per;
-                    const int ns = run(sl, off, &km, &lv);
+                    const int ns = run(sl, off, &km, &lv, &pm);
                     std::lock_guard<std::mutex> lk(mu);
                     kms += km;
+                    pms += pm;
                     levels = std::max(levels, lv);
-                    if (on_pass) on_pass(off, ns, sl.dist.p);
+                    if (on_pass) on_pass(off, ns, sl.dist.p, parents ? sl.par.p : nullptr);
                 }
             } catch (...) {
                 errs[(size_t)k] = std::current_exception();
@@ -847,7 +1111,19 @@ void msbfs_each(Graph& g, const int64_t* sources, int n_src, const MsPassFn& on_
     st.levels = levels;
     st.wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     g.stats = st;
+    if (parents_ms) *parents_ms += pms;
     // the per-source result of the last pass's final source is not kept in g.dist
+}
+
+void msbfs_each(Graph& g, const int64_t* sources, int n_src, const MsPassFn& on_pass) {
+    MsParentPassFn f;
+    if (on_pass) f = [&](int off, int ns, const int32_t* rows, const int32_t*) { on_pass(off, ns, rows); };
+    ms_run(g, sources, n_src, f, false, nullptr);
+}
+
+void msbfs_each_parents(Graph& g, const int64_t* sources, int n_src, const MsParentPassFn& on_pass,
+                        double* parents_ms) {
+    ms_run(g, sources, n_src, on_pass, true, parents_ms);
 }
 
 void msbfs_solve(Graph& g, const int64_t* sources, int n_src, int32_t* dist_out) {

@@ -12,7 +12,9 @@
 // dist[u] == dist[v] and h(u) == h(v) - 1. Every parent step lowers (dist, h),
 // so the tree is acyclic with zero weights too; it is a function of the
 // distances alone, identical for every solver path (BFS levels, delta bands,
-// either direction) and for a CPU restatement.
+// either direction) and for a CPU restatement. parent_row builds it for any distance
+// row of the graph on any stream (the batch paths' predecessor rows, int32);
+// parent_tree is the single-source caller (g.dist, the ctx stream, int64).
 //
 // Validation (the Graph500 BFS / SSSP checks, restated for the capped int32
 // distances of the reference), against the graph's CSR and the
@@ -116,6 +118,8 @@ __global__ void parent_out_k(const u32* __restrict__ par, i64 n, i64 source, int
         out[v] = v == source ? source : (par[v] == 0xffffffffu ? -1 : (int64_t)par[v]);
 }
 
+__global__ void parent_source_k(int32_t* __restrict__ out, i64 source) { out[source] = (int32_t)source; }
+
 template <typename Off, bool W>
 __global__ __launch_bounds__(256) void tree_edges_k(const Off* __restrict__ row, const u32* __restrict__ col,
                                                     const u32* __restrict__ wt, const int32_t* __restrict__ dist,
@@ -186,36 +190,37 @@ __global__ void cycle_k(const int32_t* __restrict__ dist, const int64_t* __restr
 
 unsigned grid_of(const Graph& g, i64 work) { return grid_for(work, 256, (unsigned)g.ctx->cu_count * 8u); }
 
+// dist: the distance row, par: n u32 preset to 0xffffffff, both on stream s
 template <typename Off, bool W>
-void parent_run(Graph& g, i64 source, u32* par) {
+void parent_run(Graph& g, const int32_t* dist, i64 source, u32* par, hipStream_t s, ParentWs& ws) {
     const Off* row = static_cast<const Off*>(g.row_ptr());
-    hipStream_t s = g.ctx->stream;
-    DevBuf<u32> flag(1);
-    PinnedBuf<u32> hflag;
-    hflag.alloc(1);
-    PJ_HIP(hipMemsetAsync(flag.p, 0, sizeof(u32), s));
-    parent_k<Off, W><<<grid_of(g, g.n), 256, 0, s>>>(row, g.col.p, g.w.p, g.dist.p, g.n, par, flag.p);
+    ws.flag.ensure(4);  // [0] zero-weight tight edges seen, [1..3] the level ring
+    if (!ws.hflag.p) ws.hflag.alloc(1);
+    u32* flag = ws.flag.p;
+    PJ_HIP(hipMemsetAsync(flag, 0, sizeof(u32), s));
+    parent_k<Off, W><<<grid_of(g, g.n), 256, 0, s>>>(row, g.col.p, g.w.p, dist, g.n, par, flag);
     PJ_LAUNCH_CHECK();
     if constexpr (W) {
-        PJ_HIP(hipMemcpyAsync(hflag.p, flag.p, sizeof(u32), hipMemcpyDeviceToHost, s));
+        PJ_HIP(hipMemcpyAsync(ws.hflag.p, flag, sizeof(u32), hipMemcpyDeviceToHost, s));
         PJ_HIP(hipStreamSynchronize(s));
-        if (!hflag.p[0]) return;
-        DevBuf<u32> hop((size_t)g.n), flags(3);
-        hop_init_k<<<grid_of(g, g.n), 256, 0, s>>>(par, g.n, source, hop.p);
+        if (!ws.hflag.p[0]) return;
+        ws.hop.ensure((size_t)g.n);
+        u32* flags = ws.flag.p + 1;
+        hop_init_k<<<grid_of(g, g.n), 256, 0, s>>>(par, g.n, source, ws.hop.p);
         PJ_LAUNCH_CHECK();
         const u32 f0[3] = {0, 0, 1};  // "level -1" parented something
-        PJ_HIP(hipMemcpyAsync(flags.p, f0, sizeof(f0), hipMemcpyHostToDevice, s));
+        PJ_HIP(hipMemcpyAsync(flags, f0, sizeof(f0), hipMemcpyHostToDevice, s));
         // levels in batches of 8 between host checks (a level whose predecessor parented
         // nothing exits at once); ends when a level parents nothing
         for (u32 lvl = 0;;) {
             for (int b = 0; b < 8; ++b, ++lvl) {
-                parent_zero_k<Off><<<grid_of(g, g.n), 256, 0, s>>>(row, g.col.p, g.w.p, g.dist.p, g.n, lvl, hop.p,
-                                                                   par, flags.p);
+                parent_zero_k<Off><<<grid_of(g, g.n), 256, 0, s>>>(row, g.col.p, g.w.p, dist, g.n, lvl, ws.hop.p, par,
+                                                                   flags);
                 PJ_LAUNCH_CHECK();
             }
-            PJ_HIP(hipMemcpyAsync(hflag.p, flags.p + (lvl - 1) % 3, sizeof(u32), hipMemcpyDeviceToHost, s));
+            PJ_HIP(hipMemcpyAsync(ws.hflag.p, flags + (lvl - 1) % 3, sizeof(u32), hipMemcpyDeviceToHost, s));
             PJ_HIP(hipStreamSynchronize(s));
-            if (!hflag.p[0]) break;
+            if (!ws.hflag.p[0]) break;
         }
     }
 }
@@ -229,16 +234,37 @@ void edges_run(Graph& g, const int64_t* par, u32* ok, TreeCnt* c) {
 
 }  // namespace
 
+// The parents of the distance row `dist` (device, n int32, in input ids) as n u32 in par
+// (0xffffffff = none; the source's entry is not set), enqueued on s. Weighted graphs: the
+// host waits on s for the zero-weight flags. ws is the caller's scratch: one per stream in use.
+static void parent_row_u32(Graph& g, const int32_t* dist, i64 source, u32* par, hipStream_t s, ParentWs& ws) {
+    PJ_HIP(hipMemsetAsync(par, 0xff, 4 * (size_t)g.n, s));
+    const bool w = g.weighted;
+    if (g.off64 && w) parent_run<u64, true>(g, dist, source, par, s, ws);
+    else if (g.off64) parent_run<u64, false>(g, dist, source, par, s, ws);
+    else if (w) parent_run<u32, true>(g, dist, source, par, s, ws);
+    else parent_run<u32, false>(g, dist, source, par, s, ws);
+}
+
+// int32 form (the batch rows): 0xffffffff is -1 already, so the row is written in place
+// and only parent[source] = source is added (n <= INT32_MAX, checked by the caller)
+void parent_row(Graph& g, const int32_t* dist, i64 source, int32_t* out, hipStream_t s, ParentWs& ws) {
+    if (g.n == 0) return;
+    parent_row_u32(g, dist, source, reinterpret_cast<u32*>(out), s, ws);
+    if (source >= 0 && source < g.n) {
+        parent_source_k<<<1, 1, 0, s>>>(out, source);
+        PJ_LAUNCH_CHECK();
+    }
+}
+
 void parent_tree(Graph& g, i64 source, int64_t* host_out) {
     const i64 n = g.n;
     if (n == 0) return;
     hipStream_t s = g.ctx->stream;
     DevBuf<u32> par((size_t)n);
     DevBuf<int64_t> out((size_t)n);
-    PJ_HIP(hipMemsetAsync(par.p, 0xff, 4 * (size_t)n, s));
-    const bool w = g.weighted;
-    if (g.off64) w ? parent_run<u64, true>(g, source, par.p) : parent_run<u64, false>(g, source, par.p);
-    else w ? parent_run<u32, true>(g, source, par.p) : parent_run<u32, false>(g, source, par.p);
+    ParentWs ws;
+    parent_row_u32(g, g.dist.p, source, par.p, s, ws);
     parent_out_k<<<grid_of(g, n), 256, 0, s>>>(par.p, n, source, out.p);
     PJ_LAUNCH_CHECK();
     PJ_HIP(hipMemcpyAsync(host_out, out.p, 8 * (size_t)n, hipMemcpyDeviceToHost, s));
